@@ -7,19 +7,26 @@ tol = 0 (fixed iteration count). One step = one CG iteration: the SpMV
 host sync inside a chunk (kry_cg_preferred_chunk: 32 iterations here, 256 on
 the persistent small-n loop of cfg2).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--quick] [--configs]
-                  [--workload metric|cfg4] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                  [--full] [--configs] [--workload metric|cfg4] [--no-cpu]
+
+A plain run does only what the headline needs: it builds and uploads the
+matrix, warms up, times one region of exactly K iterations, writes the
+iterate and the residual norms of that region with --dump-outputs, and prints
+the result line. Everything else below (the roofline passes, cfg4 beside the
+metric, the other legs, the CPU baseline, five timed regions instead of one)
+runs under --full.
 
 N > 1 (launched by torch.distributed.run): each rank solves its own RHS
 columns of the same matrix on its own GPU (RHS sharding) with
 one RCCL allreduce of the residual-norm vector per iteration for the global
-stop rule; value = total RHS-iterations per second (weak scaling). Unless
---quick, every N also times cfg4 (Poisson 3163^2, 8 RHS per GPU, the
+stop rule; value = total RHS-iterations per second (weak scaling). With
+--full, every N also times cfg4 (Poisson 3163^2, 8 RHS per GPU, the
 BASELINE multi-GPU configuration) the same way ("cfg4_sharded");
 --workload cfg4 makes it the headline.
 
-roofline: the CG SpMV kernel's bytes per launch are the bytes its image must
-move (the DIA image has no index stream; the compact SELL image 2 B of index
+roofline (--full): the CG SpMV kernel's bytes per launch are the bytes its
+image must move (the DIA image has no index stream; the compact SELL image 2 B of index
 per slot), divided by its average launch time from HIP events on the solver
 stream in a dedicated pass after the timed region (every launch of >= 64
 iterations); SURVEY's int32-CSR bytes S over the same time is reported
@@ -27,7 +34,7 @@ beside it as effective_gbs / frac_vs_csr_S. spmv_general repeats the
 measurement on the same matrix with the DIA image disabled (KRY_SPMV_DIA=0):
 the compact SELL kernel that arbitrary sorted CSR takes.
 
-Also reported (N = 1): GMRES(30) on the cfg3 matrix and on the metric
+Also reported (--full, N = 1): GMRES(30) on the cfg3 matrix and on the metric
 matrix, the reference API at the host-array boundary, the secondary BASELINE
 configs with --configs (cfg2 CG Poisson 1000^2, cfg4 block CG 8 RHS, cfg5
 weighted fp32 MINRES 200^3), and the CPU baseline: the oracle (the reference
@@ -248,12 +255,35 @@ def _cg_state(A, B, comm=None, rank=0, world=1):
 
 
 def _iterate(st, k, ncols, chunk=32):
-    done = 0
+    """k iterations in chunks; the residual norms of all of them (k x ncols)."""
+    done, rows = 0, []
     while done < k:
         s = min(chunk, k - done)
         hist = st.run(s, ncols)
         assert len(hist) == s, "solver stopped early"
+        rows.append(hist)
         done += s
+    return np.concatenate(rows) if rows else np.zeros((0, ncols))
+
+
+DUMP_X_BYTES = 48 << 20  # of the 64 MB a dump may take; the residual norms are small beside it
+
+
+def dump_outputs(path, st, resnorms):
+    """What a caller of the timed path holds after its last step, as
+    float32 / float64 .npy files under `path`: x.npy, the iterate (n x k; of
+    a larger one a fixed sample of rows, default_rng(0), ascending), and
+    resnorms.npy, the residual norms of the last timed region's steps."""
+    os.makedirs(path, exist_ok=True)
+    prob = st.prob
+    x = st.get(0)[:, : prob.kc]
+    if x.dtype not in (np.float32, np.float64):
+        x = x.astype(np.float64)
+    rows = DUMP_X_BYTES // (x.shape[1] * x.itemsize)
+    if rows < x.shape[0]:
+        x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], rows, replace=False))]
+    np.save(os.path.join(path, "x.npy"), np.ascontiguousarray(x))
+    np.save(os.path.join(path, "resnorms.npy"), np.ascontiguousarray(resnorms, dtype=np.float64))
 
 
 def comm_ranks(comm):
@@ -267,14 +297,17 @@ def comm_ranks(comm):
     return int(n.value), int(r.value)
 
 
-def run_cg_bench(A_host, rhs_of_rank, steps, warmup, job, repeats=1, roofline_launches=64, prof_ids=None):
+def run_cg_bench(A_host, rhs_of_rank, steps, warmup, job, repeats=1, roofline_launches=64, prof_ids=None,
+                 roofline=True, dump=None):
     """CG on every local rank's RHS block (rhs_of_rank(rank): n or n x k) of
     A: warmup, then `repeats` timed regions of EXACTLY `steps` iterations,
     each between barrier + device sync on both sides (max over ranks; in one
-    process the threads' common wall clock), then a separate pass of
-    max(steps, roofline_launches) iterations with HIP events around every
-    SpMV launch of the first local rank (the kernel's average launch time;
-    event records add stream time, so this pass is not a timed one)."""
+    process the threads' common wall clock); with `dump` the first local
+    rank's outputs are written there (dump_outputs); then, with `roofline`,
+    a separate pass of max(steps, roofline_launches) iterations with HIP
+    events around every SpMV launch of the first local rank (the kernel's
+    average launch time; event records add stream time, so this pass is not
+    a timed one)."""
     import krylov_amd
     from krylov_amd import _lib, distributed
     from krylov_amd.device import get_context
@@ -296,9 +329,10 @@ def run_cg_bench(A_host, rhs_of_rank, steps, warmup, job, repeats=1, roofline_la
 
     def iterate(k):
         def one(i):
-            _iterate(sts[i][0], k, ncols, chunk)
+            hist = _iterate(sts[i][0], k, ncols, chunk)
             ctxs[i].synchronize()
-        job.run_all(one)
+            return hist
+        return job.run_all(one)[0]
 
     iterate(warmup)
     elapsed = []
@@ -307,13 +341,17 @@ def run_cg_bench(A_host, rhs_of_rank, steps, warmup, job, repeats=1, roofline_la
         for c in ctxs:
             c.synchronize()
         t0 = time.perf_counter()
-        iterate(steps)
+        hist = iterate(steps)
         t1 = time.perf_counter()
         job.barrier()
         elapsed.append(job.allmax(t1 - t0))
-    ids = [_lib.PROF_SPMV] + [i for i in (prof_ids or []) if i != _lib.PROF_SPMV]
-    prof = profiled(ctxs[0], ids, lambda: iterate(max(steps, roofline_launches)))
-    cnt, spmv_ms = prof[_lib.PROF_SPMV]
+    if dump:
+        dump_outputs(dump, sts[0][0], hist)
+    prof, cnt, spmv_ms = {}, 0, None
+    if roofline:
+        ids = [_lib.PROF_SPMV] + [i for i in (prof_ids or []) if i != _lib.PROF_SPMV]
+        prof = profiled(ctxs[0], ids, lambda: iterate(max(steps, roofline_launches)))
+        cnt, spmv_ms = prof[_lib.PROF_SPMV]
     defer = sts[0][0].defer_info()
     del sts
     for c in comms:
@@ -321,7 +359,8 @@ def run_cg_bench(A_host, rhs_of_rank, steps, warmup, job, repeats=1, roofline_la
             c.close()
     layout = ops[0].layout()
     med = float(np.median(elapsed))
-    return {"elapsed": med, "elapsed_all": elapsed, "spmv_count": cnt, "spmv_avg_s": spmv_ms / max(cnt, 1) / 1e3,
+    return {"elapsed": med, "elapsed_all": elapsed, "spmv_count": cnt,
+            "spmv_avg_s": None if spmv_ms is None else spmv_ms / max(cnt, 1) / 1e3,
             "n": ops[0].n, "nnz": ops[0].nnz, "layout": layout, "rhs": ncols // job.world,
             "persistent_loop": chunk == 256, "prof": prof, "prof_iters": max(steps, roofline_launches),
             "ydefer": defer, "rccl_ranks": None if rccl is None else rccl[0]}
@@ -402,10 +441,12 @@ def cfg4_rooflines(res, steps):
     vec = n * k * 8
     ds = lay["dia_slots"]
     sb = ds * 8 + ds / 128 * 20 + 2 * vec
-    cnt, ms = res["prof"][_lib.PROF_SPMV]
-    spmv = hbm_roofline("spmv_dia_blk_kernel<double,double,2,8,SrcPlain,EpiApDot> (block DIA SpMV, k = %d)" % k,
-                        sb, ms / max(cnt, 1) / 1e3,
-                        "dia_slots*8 + dia_slots/128*20 + 2*n*k*8 (values, descriptors, p read, Ap written)", cnt)
+    spmv = None  # no per-launch pass was run (a plain run): the iteration's roofline only
+    if _lib.PROF_SPMV in res["prof"]:
+        cnt, ms = res["prof"][_lib.PROF_SPMV]
+        spmv = hbm_roofline("spmv_dia_blk_kernel<double,double,2,8,SrcPlain,EpiApDot> (block DIA SpMV, k = %d)" % k,
+                            sb, ms / max(cnt, 1) / 1e3,
+                            "dia_slots*8 + dia_slots/128*20 + 2*n*k*8 (values, descriptors, p read, Ap written)", cnt)
     D = res["ydefer"][0]
     pass_b = 3 * vec + 3 * vec + ((D + 1) / D * vec if D else 2 * vec)
     it_b = sb + pass_b
@@ -868,14 +909,16 @@ def compact(full, idx=None):
             "ms_per_step_max", "launch", "rccl_ranks", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
             "config")
     out = {k: _r(full[k]) if k.startswith(("value", "ms_per_step")) else full[k] for k in keys if k in full}
-    ro = full["roofline"]
-    out["roofline"] = {"bound": ro["bound"], "achieved": _r(ro["achieved"]), "peak": ro["peak"], "unit": ro["unit"],
-                       "frac": _r(ro["frac"], 3), "traffic": int(ro["traffic"]) if ro.get("traffic") else None,
-                       "kernel": _short(ro["kernel"]),
-                       "ms_per_launch": _r(ro["ms_per_launch"]), "bytes_per_launch": int(ro["bytes_per_launch"]),
-                       "launches_timed": ro.get("launches_timed")}
-    if ro.get("traffic_source"):
-        out["roofline"]["traffic_src"] = ro["traffic_source"].split(" ")[0]
+    ro = full.get("roofline")  # the per-launch pass of a --full run
+    if ro:
+        out["roofline"] = {"bound": ro["bound"], "achieved": _r(ro["achieved"]), "peak": ro["peak"],
+                           "unit": ro["unit"], "frac": _r(ro["frac"], 3),
+                           "traffic": int(ro["traffic"]) if ro.get("traffic") else None,
+                           "kernel": _short(ro["kernel"]),
+                           "ms_per_launch": _r(ro["ms_per_launch"]), "bytes_per_launch": int(ro["bytes_per_launch"]),
+                           "launches_timed": ro.get("launches_timed")}
+        if ro.get("traffic_source"):
+            out["roofline"]["traffic_src"] = ro["traffic_source"].split(" ")[0]
     it = full.get("iteration_roofline")
     if it:
         out["iteration_roofline"] = {"frac": _r(it["frac"], 3), "bytes": int(it.get("bytes_per_iteration", 0))}
@@ -952,16 +995,24 @@ def main():
     ap.add_argument("--m", type=int, default=216, help="stencil edge (216 = BASELINE metric)")
     ap.add_argument("--workload", choices=["metric", "cfg4"], default="metric",
                     help="headline: metric CG (1 RHS per GPU) or cfg4 block CG (8 RHS per GPU, Poisson 3163^2)")
-    ap.add_argument("--quick", action="store_true", help="headline only (no other legs, no CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its roofline pass, cfg4, the SpMV / GMRES / BiCGStab / host-boundary / "
+                         "cfg2 / cfg5 legs and the CPU baseline; --repeats defaults to 5")
+    ap.add_argument("--quick", action="store_true", help="headline only, also under --full (what a run without "
+                                                         "--full does anyway)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the headline's iterate and the residual norms of its last "
+                         "timed region as DIR/x.npy and DIR/resnorms.npy (at most 64 MB; see dump_outputs)")
     ap.add_argument("--configs", action="store_true",
-                    help="also time cfg4 as a plain 8-RHS block CG (and cfg2 / cfg5 under --quick; the full run has them)")
+                    help="also time cfg4 as a plain 8-RHS block CG (and cfg2 / cfg5 unless --full has them)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--full-out", default=None, help="also write the verbose JSON line (formulas, timings) here")
     ap.add_argument("--launch", choices=["auto", "threads"], default="auto",
                     help="auto: torchrun if WORLD_SIZE is set, else threads for --gpus > 1; threads: force the "
                          "one-process threaded path (also at --gpus 1, a rehearsal with a 1-rank communicator)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps iterations each; the line reports their median (min and max beside)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps iterations each (default 1; 5 under --full); the line reports "
+                         "their median (min and max beside)")
     args = ap.parse_args()
 
     from krylov_amd import _lib
@@ -972,7 +1023,9 @@ def main():
     job = Job(plan)
     world, rank = job.world, job.rank
     os.environ["KRYLOV_DEVICE"] = str(job.local)
-    repeats = max(1, args.repeats)
+    full = args.full and not args.quick
+    repeats = max(1, args.repeats if args.repeats is not None else (5 if full else 1))
+    dump = args.dump_outputs if rank == 0 else None
 
     from krylov_amd import problems
 
@@ -980,17 +1033,19 @@ def main():
     n, nnz = A_host.shape[0], int(A_host.nnz)
     P3 = None
     cfg4 = None
-    if args.workload == "cfg4" or not args.quick:
+    if args.workload == "cfg4" or full:
         P3 = problems.poisson2d(3163)
         cfg4 = run_cg_bench(P3, lambda r: cfg4_rhs(P3.shape[0], r), min(args.steps, 40), min(args.warmup, 5), job,
-                            repeats=repeats, roofline_launches=16, prof_ids=[_lib.PROF_UPDATE, _lib.PROF_OTHER])
+                            repeats=repeats, roofline_launches=16, prof_ids=[_lib.PROF_UPDATE, _lib.PROF_OTHER],
+                            roofline=full, dump=dump if args.workload == "cfg4" else None)
     if args.workload == "cfg4":
         res, hn, hnnz = cfg4, P3.shape[0], int(P3.nnz)
         workload = (f"krylov.cg block CG, 2-D 5-point Poisson 3163^2, {cfg4['rhs']} RHS per GPU (BASELINE cfg4), "
                     "tol=0 fixed iterations")
         steps_timed = min(args.steps, 40)
     else:
-        res = run_cg_bench(A_host, lambda _r: np.ones(n), args.steps, args.warmup, job, repeats=repeats)
+        res = run_cg_bench(A_host, lambda _r: np.ones(n), args.steps, args.warmup, job, repeats=repeats,
+                           roofline=full, dump=dump)
         hn, hnnz = n, nnz
         workload = f"krylov.cg, 3-D 15-point stencil {args.m}^3, one RHS per GPU, tol=0 fixed iterations"
         steps_timed = args.steps
@@ -998,14 +1053,17 @@ def main():
     rhs = res["rhs"]
     if args.workload == "cfg4":
         roof, it_roof = cfg4_rooflines(res, steps_timed)
-        t, src = leg_traffic(traffic_index(), "cfg4", "spmv", hn, hnnz)
-        roof["traffic"], roof["traffic_source"] = t, src
+        if roof is not None:
+            t, src = leg_traffic(traffic_index(), "cfg4", "spmv", hn, hnnz)
+            roof["traffic"], roof["traffic_source"] = t, src
     else:
-        t, src = leg_traffic(traffic_index(), "metric_cg", "spmv", hn, hnnz)
-        roof = roofline_of(res, hn, hnnz, {"traffic_bytes_per_launch": t, "source": src} if t else None)
+        roof = None
+        if full:
+            t, src = leg_traffic(traffic_index(), "metric_cg", "spmv", hn, hnnz)
+            roof = roofline_of(res, hn, hnnz, {"traffic_bytes_per_launch": t, "source": src} if t else None)
         # the iteration: the SpMV's image bytes + the one-launch update
         # (cg_upd_kernel: r, y, p read and written, Ap read = 7 n 8 B)
-        it_b = roof["bytes_per_launch"] + 7 * hn * 8
+        it_b = spmv_kernel_desc(res["layout"], hn)[1] + 7 * hn * 8
         t_it = T / steps_timed
         it_roof = {"bound": "hbm", "achieved": it_b / t_it / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                    "frac": it_b / t_it / 1e9 / HBM_PEAK_GBS, "bytes_per_iteration": it_b,
@@ -1041,11 +1099,10 @@ def main():
                        "threads": "one process, one host thread per GPU, ncclCommInitAll",
                        "single": "one GPU"}[job.mode],
         },
-        "spmv_gbs": roof["achieved"],
-        "spmv_ms": roof["ms_per_launch"],
-        "roofline": roof,
         "iteration_roofline": it_roof,
     }
+    if roof is not None:
+        out.update(spmv_gbs=roof["achieved"], spmv_ms=roof["ms_per_launch"], roofline=roof)
     if cfg4 is not None and args.workload != "cfg4":
         c4 = P3.shape[0]
         out["cfg4_sharded"] = {
@@ -1065,7 +1122,7 @@ def main():
         out["cfg4_sharded"]["roofline"] = c4_spmv
         out["cfg4_sharded"]["iteration_roofline"] = c4_it
     del P3
-    if world == 1 and not args.quick and args.workload == "metric":
+    if world == 1 and full and args.workload == "metric":
         out["spmv_general"] = run_spmv_general(A_host, args.steps)
         out["spmv_unstructured"] = run_spmv_unstructured(A_host, min(args.steps, 64))
         R3 = problems.random_nonsym(2_000_000)
@@ -1089,11 +1146,11 @@ def main():
         extra["cfg4_blockcg_8rhs_per_gpu"] = run_cg_config(P3, B, 20, 3)
         extra["cfg4_blockcg_8rhs_per_gpu"].pop("layout")
         del P3, B
-        if args.quick:
+        if not full:
             extra["cfg2"] = run_cfg2()
             extra["cfg5"] = run_minres_cfg5()
         out["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu and not args.quick and args.workload == "metric":
+    if rank == 0 and world == 1 and not args.no_cpu and full and args.workload == "metric":
         out["cpu_baseline"] = cpu_baseline(A_host)
     if rank == 0:
         if args.full_out:

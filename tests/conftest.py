@@ -15,10 +15,9 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    from tests import golden_io
 
-    d = os.path.join(REPO, "tests", "golden")
-    return {name: np.load(os.path.join(d, f"{name}.npz")) for name in ("solvers", "spmv", "lartg")}
+    return {name: golden_io.load(name) for name in ("solvers", "spmv", "lartg")}
 
 
 @pytest.fixture(scope="session")

@@ -12,9 +12,12 @@ read-only. It calls two names NumPy 2 removed (``np.find_common_type`` at
 source is copied: only inputs and outputs are stored.
 
 Outputs (``tests/golden/``):
-  spmv.npz        SciPy csr_matvec / csr_matvecs on adversarial CSR (bitwise)
+  spmv.npz, spmv_i64.npz
+                  SciPy csr_matvec / csr_matvecs on adversarial CSR (bitwise)
   lartg.npz       scipy dlartg / slartg and krylov.givens on edge-case pairs
-  solvers.npz     cg / gmres / minres histories and solutions on small problems
+  solvers.npz, solvers_block.npz
+                  cg / gmres / minres histories and solutions on small problems
+                  (both pairs: one fixture in two parts, tests/golden_io.py)
   precond.npz     the same with preconditioners M, Ml, Mr (make_precond)
   arnoldi.npz     cg(return_arnoldi=True) Lanczos relations (make_arnoldi)
   problems.json   SHA-256 of the generated BASELINE matrices
@@ -47,6 +50,7 @@ def _load_problems():
 
 
 problems = _load_problems()
+from tests import golden_io  # noqa: E402
 
 
 def _import_reference():
@@ -111,7 +115,7 @@ def make_spmv():
             out[f"{key}_y"] = A @ x
             out[f"{key}_X"] = X
             out[f"{key}_Y"] = A @ X
-    np.savez_compressed(os.path.join(HERE, "spmv.npz"), **out)
+    golden_io.save("spmv", out)
 
 
 def make_lartg(krylov):
@@ -235,7 +239,7 @@ def make_solvers(krylov):
     _info_arrays("cg_w20_weighted", sol, info, out)
     out.update(make_weighted_spd(krylov))
 
-    np.savez_compressed(os.path.join(HERE, "solvers.npz"), **out)
+    golden_io.save("solvers", out)
 
 
 def make_weighted_spd(krylov):
@@ -317,11 +321,10 @@ def make_problem_hashes():
 
 if __name__ == "__main__":
     krylov = _import_reference()
-    if "--only-weighted-spd" in sys.argv:  # append to the existing solvers.npz
-        path = os.path.join(HERE, "solvers.npz")
-        out = dict(np.load(path))
+    if "--only-weighted-spd" in sys.argv:  # append to the existing solvers fixture
+        out = golden_io.load("solvers")
         out.update(make_weighted_spd(krylov))
-        np.savez_compressed(path, **out)
+        golden_io.save("solvers", out)
         sys.exit(0)
     if "--only-precond" in sys.argv:
         make_precond(krylov)

@@ -18,6 +18,8 @@ import threading
 import numpy as np
 import pytest
 
+from tests import golden_io
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 
@@ -53,7 +55,7 @@ def _worker(rank, world, port, outdir, which):
     from krylov_amd.shard import ShardLayout, drive
     from tests import shard_engines as E
 
-    d = np.load(os.path.join(HERE, "golden", "solvers.npz"))
+    d = golden_io.load("solvers")
     out = {}
     if which == "cg":
         P = problems.poisson2d(64)
@@ -112,7 +114,7 @@ def _spawn(tmp_path, which, world):
 def test_sharded_cg_reproduces_block_cg_bitwise(tmp_path, world):
     """8 columns over 2 or 4 ranks: the reference's block-CG fixture bit for
     bit (the per-column recurrences are independent; sharding changes no bit)."""
-    d = np.load(os.path.join(HERE, "golden", "solvers.npz"))
+    d = golden_io.load("solvers")
     outs = _spawn(tmp_path, "cg", world)
     for o in outs:
         assert bool(o["success"]) and int(o["k"]) == int(d["cg_poisson64_blk8_numsteps"])
@@ -124,7 +126,7 @@ def test_sharded_cg_uneven_split_reproduces_block_cg(tmp_path):
     """8 columns over 3 ranks (3 + 3 + 2 real, the last rank padded with a zero
     column that the layout leaves out of the history and the stop rule, as
     krylov_amd.multi splits a block): the block-CG fixture bit for bit."""
-    d = np.load(os.path.join(HERE, "golden", "solvers.npz"))
+    d = golden_io.load("solvers")
     outs = _spawn(tmp_path, "cg_uneven", 3)
     for o in outs:
         assert bool(o["success"]) and int(o["k"]) == int(d["cg_poisson64_blk8_numsteps"])
@@ -138,7 +140,7 @@ def test_sharded_gmres_global_rules(tmp_path):
 
     world = 3
     outs = _spawn(tmp_path, "gmres", world)
-    d = np.load(os.path.join(HERE, "golden", "solvers.npz"))
+    d = golden_io.load("solvers")
     R = problems.random_nonsym(5000)
     _, blk = krylov_ref.gmres(R, d["rand5k_B3"], maxiter=60, tol=1e-6)
     ref_res = np.asarray(d["gmres_rand5k_blk3_resnorms"])

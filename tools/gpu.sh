@@ -10,8 +10,8 @@
 #   tests:F1,F2,...     pytest -m gpu on those files (-v -s, printed headroom logged)
 #   suite               the whole -m gpu suite
 #   smoke               __graft_entry__.smoke()
-#   bench[:ARGS]        python bench.py ARGS            (bench.log / bench.json)
-#   prof[:ARGS]         rocprofv3 --kernel-trace --stats over bench.py ARGS --no-cpu
+#   bench[:ARGS]        python bench.py ARGS            (bench.log / bench.json; ARGS = --full: every leg)
+#   prof[:ARGS]         rocprofv3 --kernel-trace --stats over bench.py ARGS --full --no-cpu
 #   torchrun[:ARGS]     bench.py through torch.distributed.run, 1 rank
 #   py:SECS:SCRIPT ARGS python3 SCRIPT ARGS under a SECS limit (tools/*.py probes)
 #   bin:SECS:BIN ARGS   a built probe binary (tools/dia_bench ...) under a SECS limit
@@ -44,7 +44,7 @@ for step in "$@"; do
       rc=$?; tail -1 "$log" > "$OUT/bench_$i.json"; tail -c 1500 "$log"; echo ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/prof_$i" -o bench -- python3 "$GRAFT_REPO_ROOT/bench.py" $arg --no-cpu > "$log" 2>&1)
+        -d "$OUT/prof_$i" -o bench -- python3 "$OLDPWD/bench.py" $arg --full --no-cpu > "$log" 2>&1)
       rc=$?; tail -c 600 "$log"; echo ;;
     torchrun)
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
