@@ -38,6 +38,7 @@ typedef struct kry_gmres kry_gmres;
 typedef struct kry_minres kry_minres;
 typedef struct kry_comm kry_comm;
 typedef struct kry_prog kry_prog;
+typedef struct kry_tri kry_tri;
 
 /* value / index types */
 enum { KRY_F32 = 1, KRY_F64 = 2 };
@@ -273,6 +274,51 @@ int kry_prog_lincomb(kry_prog *p, int32_t form, kry_vec *z, kry_vec *x, kry_vec 
                      int32_t rb, double sb, int32_t step);
 int kry_prog_spmv(kry_prog *p, kry_csr *A, kry_vec *x, kry_vec *y, int32_t step);
 int kry_prog_check(kry_prog *p, int32_t r, int32_t mode, int32_t step);
+/* Chain steps of the stationary solvers (stationary.py:11-157; driven by
+ * krylov_amd/stationary.py):
+ * rowscale: z = x / d (mul = 0) or z = x * d (mul = 1) with d an (n,) vector
+ *         of the vectors' dtype broadcast over the columns (jacobi's
+ *         `(r.T / D).T`, stationary.py:21; ssor's `(y.T * d).T`, :78, :90).
+ * permute: kry_csr_permute as a chain step (a renumbered A: the residual
+ *         leaves the operator's numbering before a triangular solve in the
+ *         caller's numbering, and the update re-enters it). src != dst.
+ * trisolve: kry_tri_solve as a chain step. */
+int kry_prog_rowscale(kry_prog *p, int32_t mul, kry_vec *z, kry_vec *x, kry_vec *d, int32_t step);
+int kry_prog_permute(kry_prog *p, const kry_csr *A, const kry_vec *src, kry_vec *dst, int32_t to_operator,
+                     int32_t step);
+int kry_prog_trisolve(kry_prog *p, const kry_tri *T, const kry_vec *y, kry_vec *x, int32_t step);
+
+/* ---- sparse triangular solve ------------------------------------------------
+ * x = T^-1 y for a sparse triangular T (lower != 0: lower, else upper) in CSR
+ * with strictly sorted rows and the diagonal stored; values of the vectors'
+ * dtype. Replaces scipy spsolve_triangular in gauss_seidel / sor / ssor
+ * (stationary.py:26-94). Row i is x_i = (y_i - sum_j T_ij x_j) / T_ii, the sum
+ * one term at a time in stored order, a true division, no FMA: bitwise
+ * repeatable and independent of the launch plan and of k (<= 64 columns, a
+ * power of two). x may alias y.
+ * Analysis (host): level[i] = 1 + max(level[j]) over row i's off-diagonal
+ * columns; rows ordered by (level, row) and cut into slices of up to 64 rows
+ * that never straddle a level (SELL-64 style, slice width = its longest
+ * off-diagonal row). Launch plan: consecutive levels holding at most 1024 rows
+ * together are one launch of one workgroup (workgroup barriers between the
+ * levels); a larger level is a launch of its own over many workgroups. No
+ * kernel waits on another workgroup: stream order is the only dependency
+ * between launches.
+ * kry_tri_plan (host-only, no device): info[0..4] = levels, launches, slices,
+ * slots, rows of the largest level; when non-null: level[n] (from 1), order[n]
+ * (rows by (level, row)), launch[launches + 1] (launch q runs levels
+ * [launch[q], launch[q + 1]), counted from 0), widths[slices]. Call once with
+ * null arrays to size them. A row without a diagonal entry is KRY_ESINGULAR,
+ * an entry on the wrong side of the diagonal or an unsorted row KRY_EINVAL.
+ * kry_tri_create: analysis + upload (a zero diagonal value: KRY_ESINGULAR).
+ * kry_tri_info: info[0..5] = the five values above and the image's bytes. */
+int kry_tri_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int lower, int64_t *info,
+                 int32_t *level, int32_t *order, int32_t *launch, int32_t *widths);
+int kry_tri_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,
+                   int dtype, int itype, int lower, kry_tri **out);
+int kry_tri_destroy(kry_tri *T);
+int kry_tri_info(const kry_tri *T, int64_t *info);
+int kry_tri_solve(kry_ctx *ctx, const kry_tri *T, const kry_vec *y, kry_vec *x);
 
 /* Batched LAPACK >= 3.10 ?lartg on device (givens.py:35-40); host arrays of
  * `count` values of `dtype`. Bitwise equal to scipy.linalg.lapack ?lartg. */

@@ -1,7 +1,8 @@
 """krylov_amd — MI355X-native inner loop for the Krylov solvers of
 ``ju-liu/krylov`` (cg / gmres / minres with the reference call signatures;
 bicgstab / cgs / cgr / gcr with their scalars chained on the device, over the
-same kernels).
+same kernels; richardson / jacobi / gauss_seidel / sor / ssor / chebyshev on
+the same chain, the triangular three over a device sparse triangular solve).
 
 The per-iteration work (CSR SpMV, AXPY/scale updates, inner products and
 norms, GMRES modified Gram-Schmidt + Givens, the MINRES Lanczos/QR
@@ -19,6 +20,9 @@ from .gmres import arnoldi, gmres, gmres_restarted, multi_solve_triangular
 from .minres import lanczos, minres
 from ._lib import empty_cache, memory_stats
 from .sparse import CsrOperator, as_device_operator, clear_operator_cache
+from .stationary import gauss_seidel, jacobi, richardson, sor, ssor
+from .chebyshev import chebyshev
+from .triangular import TriangularOperator
 
 __version__ = "0.1.0"
 
@@ -34,6 +38,13 @@ __all__ = [
     "cgs",
     "cgr",
     "gcr",
+    "richardson",
+    "jacobi",
+    "gauss_seidel",
+    "sor",
+    "ssor",
+    "chebyshev",
+    "TriangularOperator",
     "givens",
     "Householder",
     "lartg",

@@ -149,6 +149,14 @@ _SIGNATURES = {
     "kry_prog_lincomb": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, ctypes.c_double, _i32, ctypes.c_double, _i32],
     "kry_prog_spmv": [_vp, _vp, _vp, _vp, _i32],
     "kry_prog_check": [_vp, _i32, _i32, _i32],
+    "kry_prog_rowscale": [_vp, _i32, _vp, _vp, _vp, _i32],
+    "kry_prog_permute": [_vp, _vp, _vp, _vp, _i32, _i32],
+    "kry_prog_trisolve": [_vp, _vp, _vp, _vp, _i32],
+    "kry_tri_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _int, _ip64, _vp, _vp, _vp, _vp],
+    "kry_tri_create": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _pvp],
+    "kry_tri_destroy": [_vp],
+    "kry_tri_info": [_vp, _ip64],
+    "kry_tri_solve": [_vp, _vp, _vp, _vp],
     "kry_mem_stats": [_ip64],
     "kry_mem_release": [],
 }
@@ -330,6 +338,27 @@ def rs_plan(indptr, indices):
                           ptr(colrank)))
     return {"slices": int(info[1]), "slots": int(info[2]), "max_width": int(info[3]), "widths": widths,
             "colrank": colrank}
+
+
+def tri_plan(indptr, indices, lower=True):
+    """Host-only analysis of a sparse triangular solve (kry_tri_plan):
+    {"levels", "launches", "slices", "slots", "max_level", "level" (per row,
+    from 1), "order" (rows by (level, row)), "launch" (level boundaries of the
+    launches), "widths" (per slice)}."""
+    indptr = np.ascontiguousarray(indptr)
+    indices = np.ascontiguousarray(indices, dtype=indptr.dtype)
+    n, nnz = indptr.shape[0] - 1, indices.shape[0]
+    info = np.zeros(5, dtype=np.int64)
+    ip64 = info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    args = (n, nnz, ptr(indptr), ptr(indices), itype_code(indptr.dtype), 1 if lower else 0, ip64)
+    check(lib.kry_tri_plan(*args, None, None, None, None))
+    level = np.zeros(n, dtype=np.int32)
+    order = np.zeros(n, dtype=np.int32)
+    launch = np.zeros(int(info[1]) + 1, dtype=np.int32)
+    widths = np.zeros(int(info[2]), dtype=np.int32)
+    check(lib.kry_tri_plan(*args, ptr(level), ptr(order), ptr(launch), ptr(widths)))
+    return {"levels": int(info[0]), "launches": int(info[1]), "slices": int(info[2]), "slots": int(info[3]),
+            "max_level": int(info[4]), "level": level, "order": order, "launch": launch, "widths": widths}
 
 
 def csr_layout(indptr):

@@ -2,7 +2,7 @@
 // cgr, gcr, ... of the reference; krylov_amd/extra.py). Each call is one
 // stream-ordered launch evaluating exactly the NumPy expression tree of the
 // reference line it replaces, with per-column scalars handed over by value.
-#include "solver_common.hpp"
+#include "prog.hpp"
 
 using namespace kry;
 
@@ -200,22 +200,47 @@ struct OpLincombD {
   }
 };
 
+// z = x / d or z = x * d, d an n-vector broadcast over the k columns (the
+// reference's `(r.T / D).T` and `(y.T * d).T`, stationary.py:21,78)
+template <typename V>
+struct OpRowScale {
+  V *z;
+  const V *x, *d;
+  int kshift, mul;
+  __device__ __forceinline__ void operator()(int64_t e, int64_t N, double (&)[Vec16<V>::W]) const {
+    constexpr int W = Vec16<V>::W;
+    V xv[W];
+    VIO<V>::load(x, e, N, xv);
+#pragma unroll
+    for (int v = 0; v < W; ++v) {
+      const V dv = e + v < N ? d[(e + v) >> kshift] : V(1);
+      xv[v] = mul ? xv[v] * dv : xv[v] / dv;
+    }
+    VIO<V>::store(z, e, N, xv);
+  }
+};
+
+// kry_csr_permute's row gather as a chain step (idx null: a copy)
+template <int ES>
+__global__ __launch_bounds__(kBlock) void prog_permute_kernel(int64_t n, int kshift, const int32_t *__restrict__ idx,
+                                                              const char *__restrict__ src, char *__restrict__ dst,
+                                                              const Ctrl *ctrl, int step) {
+  if (halted(ctrl, step)) return;
+  typedef typename std::conditional<ES == 8, unsigned long long, unsigned>::type T;
+  const int64_t N = n << kshift;
+  const int64_t k1 = ((int64_t)1 << kshift) - 1;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) {
+    const int64_t from = idx ? (((int64_t)idx[i >> kshift] << kshift) | (i & k1)) : i;
+    reinterpret_cast<T *>(dst)[i] = reinterpret_cast<const T *>(src)[from];
+  }
+}
+
 void check_same(const kry_vec *a, const kry_vec *b, const char *what) {
   KRY_REQUIRE(a->n == b->n && a->k == b->k && a->dtype == b->dtype, KRY_EINVAL,
               std::string("shape/dtype mismatch: ") + what);
 }
 
 }  // namespace
-
-struct kry_prog {
-  kry_ctx *ctx = nullptr;
-  int nregs = 0, k = 1, cap = 0;
-  double *regs = nullptr;  // nregs x k
-  double *crit = nullptr;  // k
-  double *hist = nullptr;  // cap x k
-  double *part = nullptr;  // part_rows(k) x k (the dots' first stage)
-  Ctrl *ctrl = nullptr;
-};
 
 #define KRY_API_BEGIN try {
 #define KRY_API_END                  \
@@ -428,6 +453,55 @@ int kry_prog_spmv(kry_prog *p, kry_csr *A, kry_vec *x, kry_vec *y, int32_t step)
     launch_spmv<V, MV, I>(A, k, SrcPlain<V>{static_cast<const V *>(x->d), k}, EpiStore<V>{static_cast<V *>(y->d), k},
                           nullptr, nullptr, p->ctrl, step, p->ctx->stream);
   });
+  KRY_API_END
+}
+
+// z = x / d (mul = 0) or z = x * d (mul = 1), d an (n,) vector of x's dtype
+int kry_prog_rowscale(kry_prog *p, int32_t mul, kry_vec *z, kry_vec *x, kry_vec *d, int32_t step) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(p && z && x && d, KRY_EINVAL, "null argument");
+  check_same(z, x, "z / x");
+  KRY_REQUIRE(x->k == p->k, KRY_EINVAL, "column count differs from the chain's");
+  KRY_REQUIRE(d->n == x->n && d->k == 1 && d->dtype == x->dtype, KRY_EINVAL, "d must be (n,) of the vectors' dtype");
+  const int k = p->k;
+  int ks = 0;
+  while ((1 << ks) < k) ++ks;
+  const int64_t N = x->n * (int64_t)k;
+  if (x->dtype == KRY_F64)
+    launch_elementwise<double>(N, k,
+                               OpRowScale<double>{static_cast<double *>(z->d), static_cast<const double *>(x->d),
+                                                  static_cast<const double *>(d->d), ks, mul != 0},
+                               nullptr, p->ctrl, step, p->ctx->stream);
+  else
+    launch_elementwise<float>(N, k,
+                              OpRowScale<float>{static_cast<float *>(z->d), static_cast<const float *>(x->d),
+                                                static_cast<const float *>(d->d), ks, mul != 0},
+                              nullptr, p->ctrl, step, p->ctx->stream);
+  KRY_API_END
+}
+
+// kry_csr_permute as a chain step (src != dst)
+int kry_prog_permute(kry_prog *p, const kry_csr *A, const kry_vec *src, kry_vec *dst, int32_t to_operator,
+                     int32_t step) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(p && A && src && dst, KRY_EINVAL, "null argument");
+  KRY_REQUIRE(src->n == A->n && dst->n == A->n && src->k == dst->k && src->dtype == dst->dtype, KRY_EINVAL,
+              "shape mismatch");
+  KRY_REQUIRE(src != dst && src->d != dst->d, KRY_EINVAL, "src and dst must differ");
+  KRY_REQUIRE(is_pow2(src->k), KRY_EINVAL, "k must be a power of two");
+  int ks = 0;
+  while ((1 << ks) < src->k) ++ks;
+  const int64_t N = A->n * (int64_t)src->k;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, (N + kBlock - 1) / kBlock));
+  const int32_t *idx =
+      A->renumbered ? static_cast<const int32_t *>(to_operator ? A->perm : A->iperm) : nullptr;
+  if (src->dtype == KRY_F64)
+    hipLaunchKernelGGL(prog_permute_kernel<8>, dim3(grid), dim3(kBlock), 0, p->ctx->stream, A->n, ks, idx,
+                       static_cast<const char *>(src->d), static_cast<char *>(dst->d), p->ctrl, step);
+  else
+    hipLaunchKernelGGL(prog_permute_kernel<4>, dim3(grid), dim3(kBlock), 0, p->ctx->stream, A->n, ks, idx,
+                       static_cast<const char *>(src->d), static_cast<char *>(dst->d), p->ctrl, step);
+  KRY_HIP(hipGetLastError());
   KRY_API_END
 }
 

@@ -22,6 +22,11 @@ constexpr int kPairSlice = 128;
 constexpr int kCbRows = 256;         // rows per column-blocked segment (one per thread)
 // rank-sorted SELL-128 image (kry_csr::rs_*): runs of stored entries sorted by column
 constexpr int kRsChunk = 16;
+// sparse triangular solve (kry_tri): consecutive dependency levels holding at
+// most kTriGroupRows rows together run as one launch of one workgroup (each of
+// its kBlock threads takes up to kTriGroupRows / kBlock rows of a level);
+// a level above it gets a launch of its own over many workgroups
+constexpr int kTriGroupRows = 1024;
 
 // ---------------------------------------------------------------- errors
 void set_error(const std::string &msg);

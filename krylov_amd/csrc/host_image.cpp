@@ -800,11 +800,119 @@ static void cb_plan_host(int64_t n, int64_t nnz, const I *ip, const I *ix, int64
   release_later(vals);
 }
 
+// ------------------------------------------- sparse triangular solve plan
+template <typename I>
+void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriPlan &p) {
+  check_csr(n, nnz, ip, ix);
+  KRY_REQUIRE(n < INT32_MAX - kSlice, KRY_EUNSUPPORTED, "the triangular image numbers rows in int32");
+  p = TriPlan();
+  p.n = n;
+  p.level.assign((size_t)n, 0);
+  // levels: a lower triangle's rows depend on earlier rows, an upper one's on later rows
+  int32_t nlev = 0;
+  for (int64_t q = 0; q < n; ++q) {
+    const int64_t i = lower ? q : n - 1 - q;
+    int32_t lev = 1;
+    bool diag = false;
+    for (int64_t e = (int64_t)ip[i]; e < (int64_t)ip[i + 1]; ++e) {
+      const int64_t j = (int64_t)ix[e];
+      KRY_REQUIRE(e == (int64_t)ip[i] || (int64_t)ix[e - 1] < j, KRY_EINVAL,
+                  "triangular rows must be sorted without duplicates");
+      if (j == i) {
+        diag = true;
+        continue;
+      }
+      KRY_REQUIRE(lower ? j < i : j > i, KRY_EINVAL, "an entry on the wrong side of the diagonal");
+      lev = std::max(lev, p.level[(size_t)j] + 1);
+    }
+    KRY_REQUIRE(diag, KRY_ESINGULAR, "singular matrix: no diagonal entry in row " + std::to_string(i));
+    p.level[(size_t)i] = lev;
+    nlev = std::max(nlev, lev);
+  }
+  p.nlevels = nlev;
+  // rows by (level, row): a counting sort
+  p.lrow.assign((size_t)nlev + 1, 0);
+  for (int64_t i = 0; i < n; ++i) ++p.lrow[(size_t)p.level[(size_t)i]];
+  for (int32_t l = 0; l < nlev; ++l) p.lrow[(size_t)l + 1] += p.lrow[(size_t)l];
+  p.order.assign((size_t)n, 0);
+  {
+    std::vector<int32_t> at(p.lrow.begin(), p.lrow.end() - (nlev ? 1 : 0));
+    for (int64_t i = 0; i < n; ++i) p.order[(size_t)at[(size_t)p.level[(size_t)i] - 1]++] = (int32_t)i;
+  }
+  // slices of up to kSlice rows inside a level
+  p.lslice.assign((size_t)nlev + 1, 0);
+  for (int32_t l = 0; l < nlev; ++l) {
+    const int64_t rows = p.lrow[(size_t)l + 1] - p.lrow[(size_t)l];
+    p.max_level_rows = std::max(p.max_level_rows, rows);
+    p.lslice[(size_t)l + 1] = p.lslice[(size_t)l] + (int32_t)((rows + kSlice - 1) / kSlice);
+  }
+  p.nslices = nlev ? p.lslice[(size_t)nlev] : 0;
+  p.swidth.assign((size_t)p.nslices, 0);
+  p.sptr.assign((size_t)p.nslices + 1, 0);
+  for (int32_t l = 0; l < nlev; ++l)
+    for (int32_t s = p.lslice[(size_t)l]; s < p.lslice[(size_t)l + 1]; ++s) {
+      const int64_t a = p.lrow[(size_t)l] + (int64_t)kSlice * (s - p.lslice[(size_t)l]);
+      const int64_t b = std::min<int64_t>(a + kSlice, p.lrow[(size_t)l + 1]);
+      int64_t w = 0;
+      for (int64_t q = a; q < b; ++q) {
+        const int64_t i = p.order[(size_t)q];
+        w = std::max<int64_t>(w, (int64_t)ip[i + 1] - (int64_t)ip[i] - 1);
+      }
+      p.swidth[(size_t)s] = (int32_t)w;
+      p.sptr[(size_t)s + 1] = p.sptr[(size_t)s] + w * kSlice;
+    }
+  p.nslots = p.sptr[(size_t)p.nslices];
+  // launches: runs of levels that fit one workgroup together, large levels alone
+  p.launch.assign(1, 0);
+  for (int32_t l = 0; l < nlev;) {
+    int64_t tot = p.lrow[(size_t)l + 1] - p.lrow[(size_t)l];
+    int32_t e = l + 1;
+    if (tot <= kTriGroupRows)
+      while (e < nlev && tot + (p.lrow[(size_t)e + 1] - p.lrow[(size_t)e]) <= kTriGroupRows) {
+        tot += p.lrow[(size_t)e + 1] - p.lrow[(size_t)e];
+        ++e;
+      }
+    p.launch.push_back(e);
+    l = e;
+  }
+}
+
+template <typename I, typename V>
+void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int32_t> &rows, hvec<V> &diag,
+              hvec<int32_t> &col, hvec<V> &val) {
+  par_fill(rows, (size_t)p.nslices * kSlice + 1, (int32_t)-1);
+  par_fill(diag, (size_t)p.nslices * kSlice + 1, V(1));
+  par_fill(col, (size_t)p.nslots + 1, (int32_t)-1);
+  par_fill(val, (size_t)p.nslots + 1, V(0));
+  for (int64_t l = 0; l < p.nlevels; ++l)
+    for (int64_t s = p.lslice[(size_t)l]; s < p.lslice[(size_t)l + 1]; ++s) {
+      const int64_t a = p.lrow[(size_t)l] + (int64_t)kSlice * (s - p.lslice[(size_t)l]);
+      const int64_t b = std::min<int64_t>(a + kSlice, p.lrow[(size_t)l + 1]);
+      for (int64_t q = a; q < b; ++q) {
+        const int64_t i = p.order[(size_t)q], r = q - a;
+        rows[(size_t)(s * kSlice + r)] = (int32_t)i;
+        int64_t j = 0;
+        for (int64_t e = (int64_t)ip[i]; e < (int64_t)ip[i + 1]; ++e) {
+          if ((int64_t)ix[e] == i) {
+            KRY_REQUIRE(dv[e] != V(0), KRY_ESINGULAR, "singular matrix: zero diagonal in row " + std::to_string(i));
+            diag[(size_t)(s * kSlice + r)] = dv[e];
+            continue;
+          }
+          const size_t slot = (size_t)(p.sptr[(size_t)s] + j * kSlice + r);
+          col[slot] = (int32_t)ix[e];
+          val[slot] = dv[e];
+          ++j;
+        }
+      }
+    }
+}
+
 // explicit instantiations: the combinations kry_csr_create dispatches
-#define KRY_HOST_I(I)                                                                                              \
+#define KRY_HOST_I(I)                                                                                             \
   template void check_csr<I>(int64_t, int64_t, const I *, const I *);                                            \
   template bool scattered<I>(int64_t, const I *, const I *);                                                     \
   template bool rcm_order<I>(int64_t, const I *, const I *, int64_t, std::vector<int32_t> &, int64_t *);          \
+  template void tri_plan<I>(int64_t, int64_t, const I *, const I *, bool, TriPlan &);                            \
   template void sell_plan<I>(int64_t, const I *, std::vector<int64_t> *, std::vector<int32_t> *, int64_t *,     \
                              int64_t *, int64_t *);                                                              \
   template bool compact_fill<I>(const std::vector<int64_t> &, const std::vector<int32_t> &, const hvec<I> &,     \
@@ -817,7 +925,9 @@ static void cb_plan_host(int64_t n, int64_t nnz, const I *ip, const I *ix, int64
   template bool pair_build<I, MV>(int64_t, const I *, const I *, const MV *, int64_t, PairHost<MV> &);          \
   template void renumber_csr<I, MV>(int64_t, const I *, const I *, const MV *, const std::vector<int32_t> &,    \
                                     hvec<I> &, hvec<I> &, hvec<MV> &);                                          \
-  template bool rs_build<I, MV>(int64_t, const I *, const I *, const MV *, int64_t, RsHost<MV> &);
+  template bool rs_build<I, MV>(int64_t, const I *, const I *, const MV *, int64_t, RsHost<MV> &);              \
+  template void tri_fill<I, MV>(const TriPlan &, const I *, const I *, const MV *, hvec<int32_t> &, hvec<MV> &,  \
+                                hvec<int32_t> &, hvec<MV> &);
 KRY_HOST_I(int32_t)
 KRY_HOST_I(int64_t)
 KRY_HOST_IM(int32_t, float)
@@ -963,6 +1073,29 @@ int kry_rs_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices,
                  colrank);
   else
     throw Error{KRY_EINVAL, "bad itype"};
+  KRY_API_END
+}
+
+int kry_tri_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int lower, int64_t *info,
+                 int32_t *level, int32_t *order, int32_t *launch, int32_t *widths) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(indptr && info && n >= 0 && nnz >= 0 && (nnz == 0 || indices), KRY_EINVAL, "bad plan arguments");
+  TriPlan p;
+  if (itype == KRY_I32)
+    tri_plan(n, nnz, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices), lower != 0, p);
+  else if (itype == KRY_I64)
+    tri_plan(n, nnz, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices), lower != 0, p);
+  else
+    throw Error{KRY_EINVAL, "bad itype"};
+  info[0] = p.nlevels;
+  info[1] = (int64_t)p.launch.size() - 1;
+  info[2] = p.nslices;
+  info[3] = p.nslots;
+  info[4] = p.max_level_rows;
+  if (level) std::copy(p.level.begin(), p.level.end(), level);
+  if (order) std::copy(p.order.begin(), p.order.end(), order);
+  if (launch) std::copy(p.launch.begin(), p.launch.end(), launch);
+  if (widths) std::copy(p.swidth.begin(), p.swidth.end(), widths);
   KRY_API_END
 }
 

@@ -158,4 +158,36 @@ struct RsHost {
 template <typename I, typename MV>
 bool rs_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_slots, RsHost<MV> &r);
 
+// Sparse triangular solve x = T^-1 y (kry_tri, tri.hip): the analysis of a
+// triangular CSR T (lower or upper, caller's numbering, strictly sorted rows
+// with the diagonal stored). level[i] = 1 + max(level[j]) over the
+// off-diagonal columns j of row i (1 without any): the rows of one level are
+// independent once every lower level is solved. `order` lists the rows by
+// (level, row); each level is cut into slices of up to kSlice rows that never
+// straddle a level (slice s of level l holds order[lrow[l] + 64 (s -
+// lslice[l]) ...)), stored SELL-style: width = the slice's longest
+// off-diagonal row, slot (j, r) at sptr[s] + 64 j + r. The launch plan groups
+// consecutive levels [launch[q], launch[q + 1]): a run holding at most
+// kTriGroupRows rows in total is one launch of one workgroup (a workgroup
+// barrier between its levels); a level above kTriGroupRows rows is a launch
+// of its own over many workgroups. No launch waits on another workgroup.
+struct TriPlan {
+  int64_t n = 0, nlevels = 0, nslices = 0, nslots = 0, max_level_rows = 0;
+  std::vector<int32_t> level;   // n, from 1
+  std::vector<int32_t> order;   // n, rows by (level, row)
+  std::vector<int32_t> lrow;    // nlevels + 1, position in order
+  std::vector<int32_t> lslice;  // nlevels + 1, first slice
+  std::vector<int32_t> swidth;  // nslices
+  std::vector<int64_t> sptr;    // nslices + 1, slots
+  std::vector<int32_t> launch;  // launches + 1, level boundaries
+};
+template <typename I>
+void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriPlan &p);
+// The image of the plan: rows[64 nslices] (-1 = padding), diag[64 nslices]
+// (1 on padding), col / val[nslots] (col -1, val 0 = padding), every row's
+// off-diagonal entries in stored order. A zero diagonal is KRY_ESINGULAR.
+template <typename I, typename V>
+void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int32_t> &rows, hvec<V> &diag,
+              hvec<int32_t> &col, hvec<V> &val);
+
 }  // namespace kry

@@ -1,0 +1,278 @@
+// Device sparse triangular solve x = T^-1 y (kry_tri): the hot path of the
+// reference's gauss_seidel / sor / ssor (scipy spsolve_triangular,
+// stationary.py:26-94; krylov_amd/stationary.py).
+//
+// The host analysis (host_image.hpp tri_plan) sorts the rows by dependency
+// level and cuts every level into SELL-64-style slices that never straddle a
+// level. Work item (slice s, row lane r, column c) computes
+//   x[row, c] = (y[row, c] - sum_j T[row, j] x[j, c]) / T[row, row]
+// with the sum taken one term at a time in the row's stored (ascending
+// column) order and a true division, no FMA: the result depends on neither
+// the launch plan, the grid nor k. Items are numbered with the k columns of a
+// row on adjacent lanes; lane groups read consecutive slots of a slot column.
+//
+// Launches (TriPlan::launch): a run of consecutive levels that fits one
+// workgroup is one launch of one workgroup with a workgroup barrier between
+// its levels (the values cross levels through global memory: same CU,
+// workgroup scope); a larger level is one launch over many workgroups. No
+// kernel waits on another workgroup: stream order is the only cross-workgroup
+// dependency.
+#include "host_image.hpp"
+#include "prog.hpp"
+
+using namespace kry;
+
+struct kry_tri {
+  kry_ctx *ctx = nullptr;
+  int64_t n = 0, nnz = 0;
+  int dtype = 0;
+  bool lower = true;
+  int64_t nlevels = 0, nslices = 0, nslots = 0, max_level_rows = 0;
+  std::vector<int32_t> launch;  // level boundaries of the launches
+  std::vector<int32_t> lslice;  // host copy (grid sizes)
+  void *d_lslice = nullptr;     // int32, nlevels + 1
+  void *d_sptr = nullptr;       // int64, nslices + 1
+  void *d_swidth = nullptr;     // int32, nslices
+  void *d_rows = nullptr;       // int32, 64 nslices (+1), -1 = padding
+  void *d_diag = nullptr;       // dtype, 64 nslices (+1)
+  void *d_col = nullptr;        // int32, nslots (+1), -1 = padding
+  void *d_val = nullptr;        // dtype, nslots (+1)
+  size_t image_bytes = 0;
+};
+
+namespace {
+
+template <typename V>
+struct TriImg {
+  const int32_t *lslice;
+  const int64_t *sptr;
+  const int32_t *swidth;
+  const int32_t *rows;
+  const V *diag;
+  const int32_t *col;
+  const V *val;
+};
+
+// one work item: row lane r of slice s, column c. x is read at rows of lower
+// levels only (written by earlier launches, or before the last barrier).
+template <typename V>
+__device__ __forceinline__ void tri_item(const TriImg<V> &T, int64_t s, int r, int c, int kshift, const V *y, V *x) {
+  const int32_t row = T.rows[s * kSlice + r];
+  if (row < 0) return;
+  const int w = T.swidth[s];
+  const int64_t base = T.sptr[s] + r;
+  V acc = V(0);
+  for (int j = 0; j < w; ++j) {
+    const int32_t col = T.col[base + (int64_t)j * kSlice];
+    if (col >= 0) {
+      const V p = T.val[base + (int64_t)j * kSlice] * x[((int64_t)col << kshift) + c];
+      acc = acc + p;
+    }
+  }
+  const int64_t o = ((int64_t)row << kshift) + c;
+  const V num = y[o] - acc;
+  x[o] = num / T.diag[s * kSlice + r];
+}
+
+// a level of its own: slices [s0, s1) over the grid
+template <typename V>
+__global__ __launch_bounds__(kBlock) void tri_level_kernel(TriImg<V> T, int s0, int s1, int kshift, const V *y, V *x,
+                                                           const Ctrl *ctrl, int step) {
+  if (halted(ctrl, step)) return;
+  const int64_t items = ((int64_t)(s1 - s0) * kSlice) << kshift;
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= items) return;
+  const int c = (int)(t & ((1 << kshift) - 1));
+  const int64_t q = t >> kshift;
+  tri_item<V>(T, s0 + (q >> 6), (int)(q & 63), c, kshift, y, x);
+}
+
+// levels [l0, l1) in one workgroup, a barrier between them
+template <typename V>
+__global__ __launch_bounds__(kBlock) void tri_group_kernel(TriImg<V> T, int l0, int l1, int kshift, const V *y, V *x,
+                                                           const Ctrl *ctrl, int step) {
+  if (halted(ctrl, step)) return;
+  for (int l = l0; l < l1; ++l) {
+    const int s0 = T.lslice[l], s1 = T.lslice[l + 1];
+    const int64_t items = ((int64_t)(s1 - s0) * kSlice) << kshift;
+    for (int64_t t = threadIdx.x; t < items; t += kBlock) {
+      const int c = (int)(t & ((1 << kshift) - 1));
+      const int64_t q = t >> kshift;
+      tri_item<V>(T, s0 + (q >> 6), (int)(q & 63), c, kshift, y, x);
+    }
+    if (l + 1 < l1) {
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+}
+
+template <typename V>
+void tri_launch(const kry_tri *T, const kry_vec *y, kry_vec *x, const Ctrl *ctrl, int step, hipStream_t st) {
+  int ks = 0;
+  while ((1 << ks) < x->k) ++ks;
+  const TriImg<V> img{static_cast<const int32_t *>(T->d_lslice), static_cast<const int64_t *>(T->d_sptr),
+                      static_cast<const int32_t *>(T->d_swidth), static_cast<const int32_t *>(T->d_rows),
+                      static_cast<const V *>(T->d_diag),         static_cast<const int32_t *>(T->d_col),
+                      static_cast<const V *>(T->d_val)};
+  const V *yd = static_cast<const V *>(y->d);
+  V *xd = static_cast<V *>(x->d);
+  for (size_t q = 0; q + 1 < T->launch.size(); ++q) {
+    const int l0 = T->launch[q], l1 = T->launch[q + 1];
+    const int64_t rows = (int64_t)(T->lslice[(size_t)l1] - T->lslice[(size_t)l0]) * kSlice;
+    if (l1 == l0 + 1 && rows > kTriGroupRows) {
+      const int64_t items = rows << ks;
+      const int64_t grid = (items + kBlock - 1) / kBlock;
+      KRY_REQUIRE(grid < (int64_t(1) << 31), KRY_EUNSUPPORTED, "a triangular level beyond the grid limit");
+      hipLaunchKernelGGL(tri_level_kernel<V>, dim3((unsigned)grid), dim3(kBlock), 0, st, img, T->lslice[(size_t)l0],
+                         T->lslice[(size_t)l1], ks, yd, xd, ctrl, step);
+    } else {
+      hipLaunchKernelGGL(tri_group_kernel<V>, dim3(1), dim3(kBlock), 0, st, img, l0, l1, ks, yd, xd, ctrl, step);
+    }
+  }
+  KRY_HIP(hipGetLastError());
+}
+
+void tri_check(const kry_tri *T, const kry_vec *y, const kry_vec *x) {
+  KRY_REQUIRE(T && y && x, KRY_EINVAL, "null argument");
+  KRY_REQUIRE(y->n == T->n && x->n == T->n && x->k == y->k && x->dtype == T->dtype && y->dtype == T->dtype, KRY_EINVAL,
+              "shape/dtype mismatch with the triangular operator");
+  KRY_REQUIRE(is_pow2(x->k) && x->k <= 64, KRY_EUNSUPPORTED, "the triangular solve handles up to 64 columns");
+}
+
+void tri_free(kry_tri *T) {
+  for (void *b : {T->d_lslice, T->d_sptr, T->d_swidth, T->d_rows, T->d_diag, T->d_col, T->d_val}) dev_free(b);
+}
+
+template <typename T>
+void *upload(const T *h, size_t count, hipStream_t st, size_t *total) {
+  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+  void *d = dev_alloc(bytes);
+  if (count) KRY_HIP(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, st));
+  *total += count * sizeof(T);
+  return d;
+}
+
+template <typename I, typename V>
+void tri_build(kry_tri *T, int64_t n, int64_t nnz, const I *ip, const I *ix, const V *dv) {
+  TriPlan p;
+  tri_plan(n, nnz, ip, ix, T->lower, p);
+  hvec<int32_t> rows, col;
+  hvec<V> diag, val;
+  tri_fill(p, ip, ix, dv, rows, diag, col, val);
+  T->nlevels = p.nlevels;
+  T->nslices = p.nslices;
+  T->nslots = p.nslots;
+  T->max_level_rows = p.max_level_rows;
+  T->launch = p.launch;
+  T->lslice = p.lslice;
+  hipStream_t st = T->ctx->stream;
+  size_t tot = 0;
+  T->d_lslice = upload(p.lslice.data(), p.lslice.size(), st, &tot);
+  T->d_sptr = upload(p.sptr.data(), p.sptr.size(), st, &tot);
+  T->d_swidth = upload(p.swidth.data(), p.swidth.size(), st, &tot);
+  T->d_rows = upload(rows.data(), rows.size(), st, &tot);
+  T->d_diag = upload(diag.data(), diag.size(), st, &tot);
+  T->d_col = upload(col.data(), col.size(), st, &tot);
+  T->d_val = upload(val.data(), val.size(), st, &tot);
+  T->image_bytes = tot;
+  KRY_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace
+
+#define KRY_API_BEGIN try {
+#define KRY_API_END                  \
+  return KRY_OK;                     \
+  }                                  \
+  catch (const kry::Error &e) {      \
+    kry::set_error(e.msg);           \
+    return e.code;                   \
+  }                                  \
+  catch (const std::exception &e) {  \
+    kry::set_error(e.what());        \
+    return KRY_EDEVICE;              \
+  }
+
+extern "C" {
+
+int kry_tri_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,
+                   int dtype, int itype, int lower, kry_tri **out) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(ctx && out && indptr && n >= 0 && nnz >= 0 && (nnz == 0 || (indices && data)), KRY_EINVAL,
+              "bad argument");
+  KRY_REQUIRE(dtype == KRY_F32 || dtype == KRY_F64, KRY_EINVAL, "dtype must be f32 or f64");
+  KRY_REQUIRE(itype == KRY_I32 || itype == KRY_I64, KRY_EINVAL, "itype must be i32 or i64");
+  KRY_HIP(hipSetDevice(ctx->device));
+  auto *T = new kry_tri();
+  T->ctx = ctx;
+  T->n = n;
+  T->nnz = nnz;
+  T->dtype = dtype;
+  T->lower = lower != 0;
+  try {
+    const bool i32 = itype == KRY_I32, f64 = dtype == KRY_F64;
+    if (i32 && f64)
+      tri_build(T, n, nnz, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices),
+                static_cast<const double *>(data));
+    else if (i32)
+      tri_build(T, n, nnz, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices),
+                static_cast<const float *>(data));
+    else if (f64)
+      tri_build(T, n, nnz, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices),
+                static_cast<const double *>(data));
+    else
+      tri_build(T, n, nnz, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices),
+                static_cast<const float *>(data));
+  } catch (...) {
+    tri_free(T);
+    delete T;
+    throw;
+  }
+  *out = T;
+  KRY_API_END
+}
+
+int kry_tri_destroy(kry_tri *T) {
+  KRY_API_BEGIN
+  if (!T) return KRY_OK;
+  (void)hipSetDevice(T->ctx->device);
+  (void)hipStreamSynchronize(T->ctx->stream);
+  tri_free(T);
+  delete T;
+  KRY_API_END
+}
+
+int kry_tri_info(const kry_tri *T, int64_t *info) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(T && info, KRY_EINVAL, "null argument");
+  info[0] = T->nlevels;
+  info[1] = (int64_t)T->launch.size() - 1;
+  info[2] = T->nslices;
+  info[3] = T->nslots;
+  info[4] = T->max_level_rows;
+  info[5] = (int64_t)T->image_bytes;
+  KRY_API_END
+}
+
+int kry_tri_solve(kry_ctx *ctx, const kry_tri *T, const kry_vec *y, kry_vec *x) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(ctx, KRY_EINVAL, "null argument");
+  tri_check(T, y, x);
+  KRY_HIP(hipSetDevice(ctx->device));
+  if (T->dtype == KRY_F64) tri_launch<double>(T, y, x, nullptr, 0, ctx->stream);
+  else tri_launch<float>(T, y, x, nullptr, 0, ctx->stream);
+  KRY_API_END
+}
+
+int kry_prog_trisolve(kry_prog *p, const kry_tri *T, const kry_vec *y, kry_vec *x, int32_t step) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(p, KRY_EINVAL, "null argument");
+  tri_check(T, y, x);
+  KRY_REQUIRE(x->k == p->k, KRY_EINVAL, "column count differs from the chain's");
+  if (T->dtype == KRY_F64) tri_launch<double>(T, y, x, p->ctrl, step, p->ctx->stream);
+  else tri_launch<float>(T, y, x, p->ctrl, step, p->ctx->stream);
+  KRY_API_END
+}
+
+}  // extern "C"

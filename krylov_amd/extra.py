@@ -168,6 +168,21 @@ class _Chain:
         check(lib.kry_prog_spmv(self.h, op.handle, x.handle, y.handle, st))
         return y
 
+    def rowscale(self, mul, z, x, d, st):
+        """z = x * d (mul) or x / d, d an (n,) vector broadcast over the columns."""
+        check(lib.kry_prog_rowscale(self.h, 1 if mul else 0, z.handle, x.handle, d.handle, st))
+        return z
+
+    def permute(self, op, src, dst, to_operator, st):
+        """CsrOperator.permute as a chain step."""
+        check(lib.kry_prog_permute(self.h, op.handle, src.handle, dst.handle, 1 if to_operator else 0, st))
+        return dst
+
+    def trisolve(self, tri, y, x, st):
+        """x = T^-1 y (TriangularOperator; vectors in the caller's numbering)."""
+        check(lib.kry_prog_trisolve(self.h, tri.handle, y.handle, x.handle, st))
+        return x
+
     def apply(self, name, x, out, st):
         """op @ x into `out` (the reference's Identity: x itself)."""
         op = self.D.prob.ops[name]
