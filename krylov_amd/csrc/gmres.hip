@@ -66,7 +66,8 @@ struct kry_gmres {
   double *gcrit = nullptr;  // total_k
   int col_offset = 0, total_k = 0;
   int mgsp_E = -1;  // persistent MGS: -1 undecided, 0 not used, else elements per thread
-  bool mgsp_large = false;  // gm_mgsl_kernel (basis streamed) rather than gm_mgsp_kernel
+  const void *mgsp_kern = nullptr;  // the kernel chosen with mgsp_E (mgsp_launch, once per solver)
+  bool mgsp_streamed = false;  // it is a gm_mgsl_kernel (basis streamed, normalising)
   bool mgsp_norm = false;   // the last launch also wrote V_{k+1} (no w / hsafe pending)
   int mgsp_grid = 0;
   int mgsp_fallbacks = 0;  // chunks finished launch per pass after a persistent MGS timeout
@@ -285,6 +286,126 @@ __device__ __forceinline__ void reduce_rows(const double *part, int P, int k, do
   block_tree_reduce(red, B, k);
 }
 
+// ---- what the persistent kernels (gm_mgsp, gm_mgsp3, gm_mgsl) have in common
+// The pass schedule of one Arnoldi step: np = sweeps (col + 1) passes, pass p
+// of sweep p / (col + 1) subtracts alpha_j V_j, j = p mod (col + 1).
+template <typename V>
+struct MgsSched {
+  const V *Vb;
+  size_t stride;
+  int col, sweeps, np;
+  __device__ __forceinline__ MgsSched(const V *Vb_, size_t stride_, int col_, int sweeps_)
+      : Vb(Vb_), stride(stride_), col(col_), sweeps(sweeps_), np(sweeps_ * (col_ + 1)) {}
+  __device__ __forceinline__ const V *sub_of(int p) const { return Vb + stride * (size_t)(p % (col + 1)); }  // V_j
+  // the vector of pass p's inner product (null = w itself, and past the last pass)
+  __device__ __forceinline__ const V *next_of(int p) const {
+    if (p >= np) return nullptr;
+    const int j = p % (col + 1), sw = p / (col + 1);
+    if (j < col) return Vb + stride * (size_t)(j + 1);
+    if (sw + 1 < sweeps) return Vb;
+    return nullptr;
+  }
+  // h[j] += alpha_j of pass p (arnoldi.py:160-161), block 0
+  __device__ __forceinline__ void h_update(double *h, const double *alpha, int k, int p) const {
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 0 && tid < k) {
+      const int j = p % (col + 1);
+      const V a = (V)alpha[tid];
+      const V prev = p <= col ? V(0) : (V)h[(int64_t)j * k + tid];
+      h[(int64_t)j * k + tid] = (double)(prev + a);
+    }
+  }
+};
+
+// Fault injection (tests, KRY_MGS_FAULT): the last block drops out of chunk
+// step (fault_step & 0xffff), as a block that never became resident: at the
+// step's start, or (KRY_MGS_FAULT_FINAL=1, bit 16; the streamed kernel) at the
+// final normalising exchange. Injecting runs also use the short spin limit.
+struct MgsFault {
+  bool here, final_exchange;
+  unsigned spin_limit;
+  __device__ __forceinline__ MgsFault(int fault_step, int step)
+      : here(fault_step >= 0 && (fault_step & 0xffff) == step && blockIdx.x == gridDim.x - 1),
+        final_exchange((fault_step >> 16) == 1),
+        spin_limit(fault_step >= 0 ? kSpinLimitFault : kSpinLimit) {}
+  __device__ __forceinline__ bool at_start() const { return here && !final_exchange; }
+};
+
+// A timed-out exchange ends the launch with w (this step's A V_k) and the
+// partial buffers as they were, and halts the rest of the chunk from this
+// step on (stop_at); kry_gmres_run reruns the step on the launch-per-pass
+// path, whose first sweep rewrites every h[j] this launch may have touched.
+__device__ __forceinline__ void mgs_abort_step(Ctrl *ctrl, int step) {
+  if (threadIdx.x == 0) atomicMin(&ctrl->stop_at, step);
+}
+
+// Optional phase trace (KRY_MGS_TRACE): thread 0's wall-clock split of the
+// passes into compute (incl. the wait for the prefetched vectors), block
+// reduction + publish, exchange wait. tacc: four words of the block's LDS.
+struct MgsTrace {
+  unsigned long long *tbuf, *tacc;
+  __device__ __forceinline__ MgsTrace(unsigned long long *tbuf_, unsigned long long *tacc_) : tbuf(tbuf_), tacc(tacc_) {
+    if (tbuf && threadIdx.x == 0) tacc[0] = tacc[1] = tacc[2] = 0;
+  }
+  __device__ __forceinline__ void mark(int ph) const {
+    if (tbuf && threadIdx.x == 0) {
+      const unsigned long long now = wall_clock64();
+      if (ph >= 0) tacc[ph] += now - tacc[3];
+      tacc[3] = now;
+    }
+  }
+  __device__ __forceinline__ void flush() const {
+    if (tbuf && threadIdx.x == 0)
+      for (int q = 0; q < 3; ++q) tbuf[blockIdx.x * 4 + q] += tacc[q];
+  }
+};
+
+// The exchange after pass p, one column: the block's partial (thread 0's
+// part1) goes out as a granule, `prefetch` issues the next pass's loads (after
+// the publish, so they travel during the sweep), wave 0 sweeps every block's
+// granule into alpha[0]. False (in every thread) on a timeout.
+struct MgsGranules {
+  unsigned long long *gr;
+  unsigned tag;
+};
+__device__ __forceinline__ MgsGranules mgs_publish1(unsigned long long *gran, int step, int p, double part1) {
+  const MgsGranules x{gran + (size_t)(p & 1) * 2 * gridDim.x, ((unsigned)(step + 1) << 12) | (unsigned)(p + 1)};
+  if (threadIdx.x == 0) publish_partial(x.gr + 2 * blockIdx.x, x.tag, part1);
+  return x;
+}
+template <class Prefetch>
+__device__ __forceinline__ bool mgs_exchange1(unsigned long long *gran, int step, int p, double part1, unsigned *bar,
+                                              Ctrl *ctrl, double *alpha, int *flag, unsigned spin_limit,
+                                              Prefetch prefetch) {
+  const MgsGranules x = mgs_publish1(gran, step, p, part1);
+  prefetch();
+  if (threadIdx.x < 64) {
+    const bool ok = sweep_partials<false, true>(x.gr, gridDim.x, x.tag, bar, ctrl, alpha, spin_limit);
+    if (threadIdx.x == 0) *flag = ok ? 1 : 0;
+  }
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane(*flag) != 0;
+}
+
+// The exchange after pass p, k > 1 columns: the block's partial row (red[0, k))
+// goes to `slot` write-through, `prefetch` issues the next pass's loads
+// between arriving and waiting (the drain in mgs_arrive must not wait for
+// them: vmcnt is in order), every block sums the G rows into alpha[0, k).
+// False (in every thread) on a timeout.
+template <class Prefetch>
+__device__ __forceinline__ bool mgs_exchange_k(double *slot, int k, int p, unsigned *bar, Ctrl *ctrl, double *red,
+                                               double *alpha, int *flag, unsigned spin_limit, Prefetch prefetch) {
+  const int tid = threadIdx.x;
+  if (tid < k) st_agent(slot + (int64_t)blockIdx.x * k + tid, red[tid]);
+  mgs_arrive(bar, (unsigned)(p + 1));
+  prefetch();
+  if (!mgs_wait(bar, (unsigned)(p + 1), ctrl, flag, spin_limit)) return false;
+  reduce_rows<kMgsBlock, true>(slot, gridDim.x, k, red);
+  if (tid < k) alpha[tid] = red[tid];
+  __syncthreads();
+  return true;
+}
+
 // One column (k = 1): the partials travel as self-validating granules
 // {tag, 32 data bits} (two per block: the double's low and high words), stored
 // write-through; no counters, no flag. Wave 0 of every block sweeps all G
@@ -294,7 +415,7 @@ __device__ __forceinline__ void reduce_rows(const double *part, int P, int k, do
 // the granule words are zeroed once per chunk.
 constexpr int kGranWords = 2 * 2 * 256;  // two pass parities x two words x G <= 256 blocks
 // barrier words for `steps` chunk steps, then the (shared) granule words
-inline size_t bar_bytes(int steps);
+inline size_t bar_bytes(int steps) { return (size_t)steps * kBarWords * 4 + (size_t)kGranWords * 8; }
 template <typename V, int E>
 __global__ __launch_bounds__(kMgsBlock) void gm_mgsp_kernel(int64_t N, int k, V *__restrict__ w,
                                                             const V *__restrict__ Vb, size_t stride, int col,
@@ -308,62 +429,32 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsp_kernel(int64_t N, int k, V 
   constexpr int NV = E / W;
   __shared__ double red[kMgsBlock * W];
   __shared__ double alpha[kMaxCols];
-  // optional phase trace (KRY_MGS_TRACE): thread 0's wall-clock split of the
-  // passes into compute (incl. the wait for the prefetched vectors), block
-  // reduction + publish, exchange wait
   __shared__ unsigned long long tacc[4];
-  auto tmark = [&](int ph) {
-    if (tbuf && threadIdx.x == 0) {
-      const unsigned long long now = wall_clock64();
-      if (ph >= 0) tacc[ph] += now - tacc[3];
-      tacc[3] = now;
-    }
-  };
-  if (tbuf && threadIdx.x == 0) tacc[0] = tacc[1] = tacc[2] = 0;
+  const MgsTrace trace(tbuf, tacc);
   __shared__ int flag;
   const int tid = threadIdx.x;
   const int G = gridDim.x;
-  // fault injection (tests, KRY_MGS_FAULT): the last block never takes part
-  // in chunk step fault_step, as a block that never became resident
-  if (fault_step == step && (int)blockIdx.x == G - 1) return;
-  const unsigned spin_limit = fault_step >= 0 ? kSpinLimitFault : kSpinLimit;
-  // A timed-out exchange ends the launch with w (this step's A V_k) and the
-  // partial buffers as they were, and halts the rest of the chunk from this
-  // step on (stop_at); kry_gmres_run reruns the step on the launch-per-pass
-  // path, whose first sweep rewrites every h[j] this launch may have touched.
-  auto abort_step = [&]() {
-    if (tid == 0) atomicMin(&ctrl->stop_at, step);
-  };
+  const MgsFault fault(fault_step, step);
+  if (fault.at_start()) return;
   const int64_t base = (int64_t)blockIdx.x * NV * kMgsBlock;
   V wr[NV][W], vc[NV][W], vn[NV][W];
   auto ld = [&](const V *src, V(&dst)[NV][W]) {
 #pragma unroll
     for (int u = 0; u < NV; ++u) VIO<V>::load(src, (base + (int64_t)u * kMgsBlock + tid) * W, N, dst[u]);
   };
-  const int np = sweeps * (col + 1);
-  auto next_of = [&](int p) -> const V * {  // the vector of pass p's inner product (null = w)
-    const int j = p % (col + 1), sw = p / (col + 1);
-    if (j < col) return Vb + stride * (size_t)(j + 1);
-    if (sw + 1 < sweeps) return Vb;
-    return nullptr;
-  };
+  const MgsSched<V> sched(Vb, stride, col, sweeps);
+  const int np = sched.np;
   ld(w, wr);
   ld(Vb, vc);
-  if (const V *q = next_of(0)) ld(q, vn);
+  if (const V *q = sched.next_of(0)) ld(q, vn);
   // alpha_0 = <V_0, w> from the SpMV's partials
   reduce_rows<kMgsBlock, false>(part0, P0, k, red);
   if (tid < k) alpha[tid] = red[tid];
   __syncthreads();
-  tmark(-1);
+  trace.mark(-1);
   for (int p = 0; p < np; ++p) {
-    const int j = p % (col + 1);
-    const bool first_sweep = p <= col;
-    if (blockIdx.x == 0 && tid < k) {  // h[j] += alpha_j (arnoldi.py:160-161)
-      const V a = (V)alpha[tid];
-      const V prev = first_sweep ? V(0) : (V)h[(int64_t)j * k + tid];
-      h[(int64_t)j * k + tid] = (double)(prev + a);
-    }
-    const V *q = next_of(p);
+    sched.h_update(h, alpha, k, p);
+    const V *q = sched.next_of(p);
     double acc[W];
 #pragma unroll
     for (int v = 0; v < W; ++v) acc[v] = 0.0;
@@ -381,7 +472,7 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsp_kernel(int64_t N, int k, V 
         }
       }
     }
-    tmark(0);
+    trace.mark(0);
     if (q) {  // V_{j+1} becomes the next pass's subtrahend
 #pragma unroll
       for (int u = 0; u < NV; ++u)
@@ -409,35 +500,25 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsp_kernel(int64_t N, int k, V 
       }
 #pragma unroll
       for (int u = 0; u < NV; ++u) VIO<V>::store(w, (base + (int64_t)u * kMgsBlock + tid) * W, N, wr[u]);
-      tmark(1);
-      if (tbuf && tid == 0)
-        for (int q3 = 0; q3 < 3; ++q3) tbuf[blockIdx.x * 4 + q3] += tacc[q3];
+      trace.mark(1);
+      trace.flush();
       return;
     }
+    // the vector after next is prefetched inside the exchange
+    auto prefetch = [&] {
+      if (const V *q2 = sched.next_of(p + 1)) ld(q2, vn);
+    };
     if (k == 1) {  // granule all-gather of the block partials
-      unsigned long long *gr = gran + (size_t)(p & 1) * 2 * G;
-      const unsigned tag = ((unsigned)(step + 1) << 12) | (unsigned)(p + 1);
-      if (tid == 0) publish_partial(gr + 2 * blockIdx.x, tag, part1);
-      tmark(1);
-      if (const V *q2 = next_of(p + 1)) ld(q2, vn);
-      if (tid < 64) {
-        const bool ok = sweep_partials<false, true>(gr, G, tag, bar, ctrl, alpha, spin_limit);
-        if (tid == 0) flag = ok ? 1 : 0;
-      }
-      __syncthreads();
-      if (!flag) return abort_step();
-      tmark(2);
+      const bool ok = mgs_exchange1(gran, step, p, part1, bar, ctrl, alpha, &flag, fault.spin_limit, [&] {
+        trace.mark(1);
+        prefetch();
+      });
+      if (!ok) return mgs_abort_step(ctrl, step);
+      trace.mark(2);
       continue;
     }
-    if (tid < k) st_agent(slot + (int64_t)blockIdx.x * k + tid, red[tid]);
-    mgs_arrive(bar, (unsigned)(p + 1));
-    // prefetch the vector after next only now: the drain in mgs_arrive must
-    // not wait for it (vmcnt is in order); it travels during the wait
-    if (const V *q2 = next_of(p + 1)) ld(q2, vn);
-    if (!mgs_wait(bar, (unsigned)(p + 1), ctrl, &flag, spin_limit)) return abort_step();
-    reduce_rows<kMgsBlock, true>(slot, G, k, red);
-    if (tid < k) alpha[tid] = red[tid];
-    __syncthreads();
+    if (!mgs_exchange_k(slot, k, p, bar, ctrl, red, alpha, &flag, fault.spin_limit, prefetch))
+      return mgs_abort_step(ctrl, step);
   }
 }
 
@@ -490,23 +571,13 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsp3_kernel(int64_t N, int k, V
   __shared__ __attribute__((aligned(16))) V nb[2][NV][kMgsBlock * W];  // partners two passes ahead
   __shared__ double red[kMgsBlock * W];
   __shared__ double alpha[kMaxCols];
-  __shared__ unsigned long long tacc[4];  // phase trace (KRY_MGS_TRACE), as gm_mgsp_kernel's
-  auto tmark = [&](int ph) {
-    if (tbuf && threadIdx.x == 0) {
-      const unsigned long long now = wall_clock64();
-      if (ph >= 0) tacc[ph] += now - tacc[3];
-      tacc[3] = now;
-    }
-  };
-  if (tbuf && threadIdx.x == 0) tacc[0] = tacc[1] = tacc[2] = 0;
+  __shared__ unsigned long long tacc[4];
+  const MgsTrace trace(tbuf, tacc);
   __shared__ int flag;
   const int tid = threadIdx.x;
   const int G = gridDim.x;
-  if (fault_step == step && (int)blockIdx.x == G - 1) return;  // KRY_MGS_FAULT (tests)
-  const unsigned spin_limit = fault_step >= 0 ? kSpinLimitFault : kSpinLimit;
-  auto abort_step = [&]() {
-    if (tid == 0) atomicMin(&ctrl->stop_at, step);
-  };
+  const MgsFault fault(fault_step, step);
+  if (fault.at_start()) return;
   const int64_t base = (int64_t)blockIdx.x * NV * kMgsBlock;
   V wr[NV][W], vc[NV][W], vn[NV][W];
   auto ld = [&](const V *src, V(&dst)[NV][W]) {
@@ -543,45 +614,31 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsp3_kernel(int64_t N, int k, V
       for (int v = 0; v < W; ++v) vn[u][v] = t[v];
     }
   };
-  const int np = sweeps * (col + 1);
-  auto next_of = [&](int p) -> const V * {  // the vector of pass p's inner product (null = w)
-    if (p >= np) return nullptr;
-    const int j = p % (col + 1), sw = p / (col + 1);
-    if (j < col) return Vb + stride * (size_t)(j + 1);
-    if (sw + 1 < sweeps) return Vb;
-    return nullptr;
-  };
-  // h[j] += alpha_j of pass p (arnoldi.py:160-161), block 0; issued where
-  // no copy of this wave is in flight (its load would wait behind them)
-  auto h_update = [&](int p) {
-    if (blockIdx.x == 0 && tid < k) {
-      const int j = p % (col + 1);
-      const V a = (V)alpha[tid];
-      const V prev = p <= col ? V(0) : (V)h[(int64_t)j * k + tid];
-      h[(int64_t)j * k + tid] = (double)(prev + a);
-    }
-  };
+  const MgsSched<V> sched(Vb, stride, col, sweeps);
+  const int np = sched.np;
   ld(w, wr);
   ld(Vb, vc);
   reduce_rows<kMgsBlock, false>(part0, P0, k, red);  // alpha_0 = <V_0, w> from the SpMV's partials
   if (tid < k) alpha[tid] = red[tid];
   __syncthreads();
-  h_update(0);
+  // (h is updated where no copy of this wave is in flight: its load would
+  // wait behind them)
+  sched.h_update(h, alpha, k, 0);
   // w, V_0 and h in: only copies from here on. (s_waitcnt encodings on gfx9:
   // vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8; the builtin, not
   // inline asm, so the compiler's own wait tracking sees it)
   __builtin_amdgcn_s_waitcnt(0x0F70);
-  if (const V *q0 = next_of(0)) dma(q0, 0);  // the partners of passes 0 and 1
-  if (const V *q1 = next_of(1)) dma(q1, 1);
-  tmark(-1);
+  if (const V *q0 = sched.next_of(0)) dma(q0, 0);  // the partners of passes 0 and 1
+  if (const V *q1 = sched.next_of(1)) dma(q1, 1);
+  trace.mark(-1);
   for (int p = 0; p < np; ++p) {
-    const V *q = next_of(p);
+    const V *q = sched.next_of(p);
     if (q) {
       // this pass's partner was copied during an earlier exchange; the copy
       // of the next pass's (NV instructions, issued since, if any) may stay
       // in flight
       static_assert(NV < 16, "vmcnt(NV) in the low field");
-      if (next_of(p + 1)) __builtin_amdgcn_s_waitcnt(0x0F70 | NV);
+      if (sched.next_of(p + 1)) __builtin_amdgcn_s_waitcnt(0x0F70 | NV);
       else __builtin_amdgcn_s_waitcnt(0x0F70);
       nb_ld(p & 1);
     }
@@ -603,7 +660,7 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsp3_kernel(int64_t N, int k, V
         }
       }
     }
-    tmark(0);
+    trace.mark(0);
     if (q) {  // V_{j+1} becomes the next pass's subtrahend
 #pragma unroll
       for (int u = 0; u < NV; ++u)
@@ -627,282 +684,29 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsp3_kernel(int64_t N, int k, V
       if (tid == 0) slot[blockIdx.x] = part1;
 #pragma unroll
       for (int u = 0; u < NV; ++u) VIO<V>::store(w, (base + (int64_t)u * kMgsBlock + tid) * W, N, wr[u]);
-      tmark(1);
-      if (tbuf && tid == 0)
-        for (int q3 = 0; q3 < 3; ++q3) tbuf[blockIdx.x * 4 + q3] += tacc[q3];
+      trace.mark(1);
+      trace.flush();
       __builtin_amdgcn_s_waitcnt(0x0F70);
       return;
     }
-    unsigned long long *gr = gran + (size_t)(p & 1) * 2 * G;
-    const unsigned tag = ((unsigned)(step + 1) << 12) | (unsigned)(p + 1);
-    if (tid == 0) publish_partial(gr + 2 * blockIdx.x, tag, part1);
-    tmark(1);
-    const V *q2 = next_of(p + 2);
+    const MgsGranules x = mgs_publish1(gran, step, p, part1);
+    trace.mark(1);
+    const V *q2 = sched.next_of(p + 2);
     if (q2 && tid >= 64) dma(q2, p & 1);  // the partner of pass p + 2 (nb[p & 1] held pass p's, now in vn / vc)
     if (tid < 64) {
-      const bool ok = sweep_partials<false, true>(gr, G, tag, bar, ctrl, alpha, spin_limit);
+      const bool ok = sweep_partials<false, true>(x.gr, G, x.tag, bar, ctrl, alpha, fault.spin_limit);
       if (tid == 0) flag = ok ? 1 : 0;
     }
     raw_barrier();
     if (!flag) {
       __builtin_amdgcn_s_waitcnt(0x0F70);  // no copy left in flight when the block leaves
-      return abort_step();
+      return mgs_abort_step(ctrl, step);
     }
     if (tid < 64) {
-      h_update(p + 1);  // (wave 0 has no copy in flight here)
+      sched.h_update(h, alpha, k, p + 1);  // (wave 0 has no copy in flight here)
       if (q2) dma(q2, p & 1);  // wave 0's rows, after its polls
     }
-    tmark(2);
-  }
-}
-
-// ------------------------------ persistent MGS with a two-vector lookahead
-// The same Arnoldi step as gm_mgsp_kernel with half the dependent grid
-// exchanges. The flattened MGS index list m = 0 .. np - 1 (vector
-// V_{m mod (col + 1)}, sweep m / (col + 1)) is split into groups {0} (alpha_0
-// from the SpMV's partials), {1, 2}, {3, 4}, ... (the last one single when
-// np - 1 is odd). Pass t subtracts group t, whose alphas are known,
-//   w -= alpha_a V_a;  w -= alpha_b V_b            (arnoldi.py:162, in order)
-// and forms the partials of group t + 1 = {a', b'} in the same sweep over w:
-//   c_a = <V_a', w>,  c_b = <V_b', w>,  g = <V_b', V_a'>
-// so ONE exchange gives alpha_a' = c_a and
-//   alpha_b' = <V_b', w - alpha_a' V_a'> = c_b - alpha_a' g
-// which is MGS in exact arithmetic (arnoldi.py:159-162); in floating point
-// alpha_b' moves by ~eps |alpha_a' g|, with g ~ eps for an orthonormal basis.
-// After the last group, <w, w> as before. Group t + 1's vectors are
-// prefetched into registers during pass t's predecessor's exchange and are
-// the subtrahends of pass t + 1 (read from HBM once per step, as in
-// gm_mgsp_kernel). KRY_MGS_LOOKAHEAD=0 restores gm_mgsp_kernel.
-__device__ __forceinline__ int la_groups(int np) { return 1 + np / 2; }
-__device__ __forceinline__ int la_first(int t) { return t == 0 ? 0 : 2 * t - 1; }
-__device__ __forceinline__ int la_size(int t, int np) {
-  return t >= la_groups(np) ? 0 : (t == 0 ? 1 : (np - (2 * t - 1) >= 2 ? 2 : 1));
-}
-// granule words: two pass parities x three values x two words x G <= 256 blocks
-constexpr int kGranWordsLa = 2 * 3 * 2 * 256;
-inline size_t bar_bytes(int steps) {
-  return (size_t)steps * kBarWords * 4 + (size_t)(kGranWords > kGranWordsLa ? kGranWords : kGranWordsLa) * 8;
-}
-
-template <typename V, int E>
-__global__ __launch_bounds__(kMgsBlock) void gm_mgsp2_kernel(int64_t N, int k, V *__restrict__ w,
-                                                             const V *__restrict__ Vb, size_t stride, int col,
-                                                             int sweeps, const double *__restrict__ part0, int P0,
-                                                             double *__restrict__ pbuf, double *__restrict__ h,
-                                                             unsigned *bar, unsigned long long *gran, Ctrl *ctrl,
-                                                             int step, int fault_step,
-                                                             unsigned long long *tbuf = nullptr) {
-  if (halted(ctrl, step)) return;
-  constexpr int W = Vec16<V>::W;
-  constexpr int NV = E / W;
-  __shared__ unsigned long long tacc[4];  // phase trace (KRY_MGS_TRACE), as gm_mgsp_kernel's
-  auto tmark = [&](int ph) {
-    if (tbuf && threadIdx.x == 0) {
-      const unsigned long long now = wall_clock64();
-      if (ph >= 0) tacc[ph] += now - tacc[3];
-      tacc[3] = now;
-    }
-  };
-  if (tbuf && threadIdx.x == 0) tacc[0] = tacc[1] = tacc[2] = 0;
-  // the current pass's subtrahends, per-thread storage (each thread reads back
-  // only what it wrote: no barrier): registers hold w and the partners only
-  __shared__ __attribute__((aligned(16))) V sub[2][NV][kMgsBlock * W];
-  __shared__ double red[kMgsBlock * W];
-  __shared__ double alpha[2 * kMaxCols];  // the current group's alphas: [i * k + column]
-  __shared__ double xs[3];                // k == 1: the exchanged sums
-  __shared__ int flags[3];
-  __shared__ int flag;
-  const int tid = threadIdx.x;
-  const int G = gridDim.x;
-  if (fault_step == step && (int)blockIdx.x == G - 1) return;  // KRY_MGS_FAULT (tests)
-  const unsigned spin_limit = fault_step >= 0 ? kSpinLimitFault : kSpinLimit;
-  auto abort_step = [&]() {
-    if (tid == 0) atomicMin(&ctrl->stop_at, step);
-  };
-  // the block's segment of every vector through a buffer descriptor (no
-  // per-granule address registers; out-of-range elements read as 0, so they
-  // add 0 to every partial, and their stores are dropped), laid out as in
-  // gm_mgsp_kernel: granule u of thread tid = elements (u B + tid) W ...
-  const int64_t seg = (int64_t)NV * kMgsBlock * W;
-  const int64_t e0 = (int64_t)blockIdx.x * seg;
-  int colv[W];  // the column of element v of every granule (strides are multiples of 1024 >= k)
-#pragma unroll
-  for (int v = 0; v < W; ++v) colv[v] = (tid * W + v) & (k - 1);
-  V wr[NV][W], ta[NV][W], tb[NV][W];
-  typedef V vec_t __attribute__((ext_vector_type(W)));
-  auto sub_ld = [&](int i, int u, V(&o)[W]) {
-    const vec_t t = *reinterpret_cast<const vec_t *>(&sub[i][u][tid * W]);
-#pragma unroll
-    for (int v = 0; v < W; ++v) o[v] = t[v];
-  };
-  auto sub_st = [&](int i, int u, const V(&o)[W]) {
-    vec_t t;
-#pragma unroll
-    for (int v = 0; v < W; ++v) t[v] = o[v];
-    *reinterpret_cast<vec_t *>(&sub[i][u][tid * W]) = t;
-  };
-  auto ld = [&](const V *src, V(&dst)[NV][W]) {
-    const BufSeg<V, kMgsBlock> sg(src, e0, N, seg);
-#pragma unroll
-    for (int u = 0; u < NV; ++u) sg.template load<W>(u, dst[u]);
-  };
-  const int np = sweeps * (col + 1);
-  const int ng = la_groups(np);
-  auto vec_of = [&](int m) -> const V * { return Vb + stride * (size_t)(m % (col + 1)); };
-  auto ld_group = [&](int t) {  // group t's vectors into ta, tb
-    const int sz = la_size(t, np);
-    if (sz >= 1) ld(vec_of(la_first(t)), ta);
-    if (sz == 2) ld(vec_of(la_first(t) + 1), tb);
-  };
-  ld(w, wr);
-  ld(Vb, ta);  // V_0, the first pass's subtrahend
-#pragma unroll
-  for (int u = 0; u < NV; ++u) sub_st(0, u, ta[u]);
-  ld_group(1);
-  reduce_rows<kMgsBlock, false>(part0, P0, k, red);  // alpha_0 = <V_0, w> from the SpMV's partials
-  if (tid < k) alpha[tid] = red[tid];
-  __syncthreads();
-  tmark(-1);
-  for (int t = 0; t < ng; ++t) {
-    const int sS = la_size(t, np), sT = la_size(t + 1, np);
-    const int m0 = la_first(t);
-    if (blockIdx.x == 0 && tid < k) {  // h[j] += alpha_j (arnoldi.py:160-161)
-      for (int i = 0; i < sS; ++i) {
-        const int m = m0 + i, j = m % (col + 1);
-        const V a = (V)alpha[i * k + tid];
-        const V prev = m <= col ? V(0) : (V)h[(int64_t)j * k + tid];
-        h[(int64_t)j * k + tid] = (double)(prev + a);
-      }
-    }
-    double acc[3][W];
-#pragma unroll
-    for (int n = 0; n < 3; ++n)
-#pragma unroll
-      for (int v = 0; v < W; ++v) acc[n][v] = 0.0;
-    V a1[W], a2[W];
-#pragma unroll
-    for (int v = 0; v < W; ++v) {
-      a1[v] = (V)alpha[colv[v]];
-      a2[v] = (V)alpha[k + colv[v]];
-    }
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      V sa[W], sb[W];
-      sub_ld(0, u, sa);
-      if (sS == 2) sub_ld(1, u, sb);
-#pragma unroll
-      for (int v = 0; v < W; ++v) {
-        wr[u][v] = wr[u][v] - a1[v] * sa[v];
-        if (sS == 2) wr[u][v] = wr[u][v] - a2[v] * sb[v];
-        const double b = (double)wr[u][v];
-        if (sT == 0) {
-          acc[0][v] += dterm(b, b);
-        } else {
-          acc[0][v] += dterm((double)ta[u][v], b);
-          if (sT == 2) {
-            acc[1][v] += dterm((double)tb[u][v], b);
-            acc[2][v] += dterm((double)tb[u][v], (double)ta[u][v]);
-          }
-        }
-      }
-    }
-    tmark(0);
-    if (sT) {  // group t + 1 becomes the next pass's subtrahends
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        sub_st(0, u, ta[u]);
-        if (sT == 2) sub_st(1, u, tb[u]);
-      }
-    }
-    const int nval = sT == 2 ? 3 : 1;
-    double pv[3] = {0.0, 0.0, 0.0};  // k == 1: the block partials, in wave 0
-    if (k == 1) {
-      double t3[3];
-#pragma unroll
-      for (int n = 0; n < 3; ++n) {
-        t3[n] = acc[n][0];
-#pragma unroll
-        for (int v = 1; v < W; ++v) t3[n] += acc[n][v];
-      }
-      if (nval == 3) {
-        block_sumn_t0_dpp<3>(t3, red + kMgsBlock);
-      } else {
-        double t1[1] = {t3[0]};
-        block_sumn_t0_dpp<1>(t1, red + kMgsBlock);
-        t3[0] = t1[0];
-      }
-#pragma unroll
-      for (int n = 0; n < 3; ++n) pv[n] = t3[n];
-    }
-    if (t == ng - 1) {  // <w, w> partials for the QR kernel; w back to HBM
-      double *slot = pbuf + (size_t)6 * G * k;
-      if (k == 1) {
-        if (tid == 0) slot[blockIdx.x] = pv[0];
-      } else {
-        __syncthreads();
-#pragma unroll
-        for (int v = 0; v < W; ++v) red[tid * W + v] = acc[0][v];
-        block_tree_reduce(red, kMgsBlock * W, k);
-        if (tid < k) slot[(int64_t)blockIdx.x * k + tid] = red[tid];
-      }
-      const BufSeg<V, kMgsBlock> ws(w, e0, N, seg);
-#pragma unroll
-      for (int u = 0; u < NV; ++u) ws.template store<W>(u, wr[u]);
-      tmark(1);
-      if (tbuf && tid == 0)
-        for (int q3 = 0; q3 < 3; ++q3) tbuf[blockIdx.x * 4 + q3] += tacc[q3];
-      return;
-    }
-    if (k == 1) {  // granule all-gather of the block partials
-      unsigned long long *gr = gran + (size_t)(t & 1) * 3 * 2 * G;
-      const unsigned tag = ((unsigned)(step + 1) << 12) | (unsigned)(t + 1);
-      if (tid == 0) {
-        if (nval == 3) publish_partials_n<3>(gr, G, tag, pv);
-        else publish_partials_n<1>(gr, G, tag, pv);
-      }
-      tmark(1);
-      ld_group(t + 2);  // travels during the wait
-      // wave v sweeps value v's granules (one wave's poll state each, as in
-      // the one-value kernels)
-      if (tid < 64 * nval) {
-        const int v = tid >> 6;
-        const bool ok = sweep_partials_n<1>(gr + (size_t)2 * v * G, G, tag, bar, ctrl, xs + v, spin_limit);
-        if ((tid & 63) == 0) flags[v] = ok ? 1 : 0;
-      }
-      __syncthreads();
-      if (!(flags[0] && (nval == 1 || (flags[1] && flags[2])))) return abort_step();
-      if (tid == 0) {
-        const V aa = (V)xs[0];
-        alpha[0] = xs[0];
-        if (nval == 3) alpha[1] = xs[1] - (double)aa * xs[2];
-      }
-      __syncthreads();
-      tmark(2);
-      continue;
-    }
-    double *slot = pbuf + (size_t)(t & 1) * 3 * G * k;
-    for (int n = 0; n < nval; ++n) {
-      __syncthreads();
-#pragma unroll
-      for (int v = 0; v < W; ++v) red[tid * W + v] = acc[n][v];
-      block_tree_reduce(red, kMgsBlock * W, k);
-      if (tid < k) st_agent(slot + ((int64_t)n * G + blockIdx.x) * k + tid, red[tid]);
-    }
-    mgs_arrive(bar, (unsigned)(t + 1));
-    ld_group(t + 2);
-    if (!mgs_wait(bar, (unsigned)(t + 1), ctrl, &flag, spin_limit)) return abort_step();
-    double xv[3] = {0.0, 0.0, 0.0};
-    for (int n = 0; n < nval; ++n) {
-      reduce_rows<kMgsBlock, true>(slot + (int64_t)n * G * k, G, k, red);
-      if (tid < k) xv[n] = red[tid];
-      __syncthreads();
-    }
-    if (tid < k) {
-      const V aa = (V)xv[0];
-      alpha[tid] = xv[0];
-      if (nval == 3) alpha[k + tid] = xv[1] - (double)aa * xv[2];
-    }
-    __syncthreads();
+    trace.mark(2);
   }
 }
 
@@ -952,16 +756,8 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsl_kernel(int64_t N, int k, V 
   __shared__ int flag;
   const int tid = threadIdx.x;
   const int G = gridDim.x;
-  // fault injection (tests, KRY_MGS_FAULT): the last block drops out at chunk
-  // step fault_step, at its start, or (KRY_MGS_FAULT_FINAL=1, bit 16) at the
-  // final normalising exchange, after the other blocks' passes are done
-  const bool fault_here = fault_step >= 0 && (fault_step & 0xffff) == step && (int)blockIdx.x == G - 1;
-  const bool fault_final = (fault_step >> 16) == 1;
-  if (fault_here && !fault_final) return;
-  const unsigned spin_limit = fault_step >= 0 ? kSpinLimitFault : kSpinLimit;
-  auto abort_step = [&]() {
-    if (tid == 0) atomicMin(&ctrl->stop_at, step);
-  };
+  const MgsFault fault(fault_step, step);
+  if (fault.at_start()) return;
   const int64_t seg = (int64_t)NV * kMgsBlock * W;  // elements of the block's segment
   const int64_t e0 = (int64_t)blockIdx.x * seg;
   // element v of every granule of this thread belongs to column (tid W + v) & (k - 1)
@@ -973,14 +769,8 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsl_kernel(int64_t N, int k, V 
   V wr[NV][W];
 #pragma unroll
   for (int u = 0; u < NV; ++u) ws.template load<W>(u, wr[u]);
-  const int np = sweeps * (col + 1);
-  auto sub_of = [&](int p) -> const V * { return Vb + stride * (size_t)(p % (col + 1)); };  // V_j of pass p
-  auto next_of = [&](int p) -> const V * {  // the vector of pass p's inner product (null = w)
-    const int j = p % (col + 1), sw = p / (col + 1);
-    if (j < col) return Vb + stride * (size_t)(j + 1);
-    if (sw + 1 < sweeps) return Vb;
-    return nullptr;
-  };
+  const MgsSched<V> sched(Vb, stride, col, sweeps);
+  const int np = sched.np;
   // chunk buffers: [parity][granule of the chunk][element]
   V cs[2][U][W], cn[2][U][W];
   auto ld_chunk = [&](const MgslSeg<V> &sg, int c, V(&dst)[U][W]) {
@@ -1007,7 +797,7 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsl_kernel(int64_t N, int k, V 
     *reinterpret_cast<vec_t *>(&keep[g][tid * W]) = t;
   };
   {
-    const MgslSeg<V> s0(sub_of(0), e0, N, seg);
+    const MgslSeg<V> s0(sched.sub_of(0), e0, N, seg);
 #pragma unroll
     for (int g = 0; g < KU; ++g) {  // V_0's kept rows
       V t[W];
@@ -1015,22 +805,16 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsl_kernel(int64_t N, int k, V 
       keep_st(g, t);
     }
     if (KC == 0) ld_chunk_sub(s0, 0, cs[0]);
-    const V *q = next_of(0);
+    const V *q = sched.next_of(0);
     ld_chunk(MgslSeg<V>(q ? q : Vb, e0, N, seg), 0, cn[0]);
   }
   reduce_rows<kMgsBlock, false>(part0, P0, k, red);  // alpha_0 = <V_0, w> from the SpMV's partials
   if (tid < k) alpha[tid] = red[tid];
   __syncthreads();
   for (int p = 0; p < np; ++p) {
-    const int j = p % (col + 1);
-    const bool first_sweep = p <= col;
-    if (blockIdx.x == 0 && tid < k) {  // h[j] += alpha_j (arnoldi.py:160-161)
-      const V a = (V)alpha[tid];
-      const V prev = first_sweep ? V(0) : (V)h[(int64_t)j * k + tid];
-      h[(int64_t)j * k + tid] = (double)(prev + a);
-    }
-    const MgslSeg<V> sv(sub_of(p), e0, N, seg);
-    const V *qp = next_of(p);
+    sched.h_update(h, alpha, k, p);
+    const MgslSeg<V> sv(sched.sub_of(p), e0, N, seg);
+    const V *qp = sched.next_of(p);
     const MgslSeg<V> sq(qp ? qp : Vb, e0, N, seg);
     V al[W];
 #pragma unroll
@@ -1106,22 +890,26 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsl_kernel(int64_t N, int k, V 
       // its registers; w itself is not written back. The QR kernel reads
       // the exchanged sum as a single partial row (slot 2, row 0).
       double *tot = pbuf + (size_t)2 * G * k;
-      if (fault_here) return;  // KRY_MGS_FAULT_FINAL: never joins the normalising exchange
+      if (fault.here) return;  // KRY_MGS_FAULT_FINAL: never joins the normalising exchange
+      // (written out, not through mgs_publish1 / mgs_exchange1 /
+      // mgs_exchange_k: with them here the register allocation of the whole
+      // kernel changes, 197 -> 205 VGPRs at NV = 12 and 56 -> 108 B of scratch
+      // at NV = 40)
       if (k == 1) {
         unsigned long long *gr = gran + (size_t)(p & 1) * 2 * G;
         const unsigned tag = ((unsigned)(step + 1) << 12) | (unsigned)(p + 1);
         if (tid == 0) publish_partial(gr + 2 * blockIdx.x, tag, part1);
         if (tid < 64) {
-          const bool ok = sweep_partials<false, true>(gr, G, tag, bar, ctrl, alpha, spin_limit);
+          const bool ok = sweep_partials<false, true>(gr, G, tag, bar, ctrl, alpha, fault.spin_limit);
           if (tid == 0) flag = ok ? 1 : 0;
         }
         __syncthreads();
-        if (!__builtin_amdgcn_readfirstlane(flag)) return abort_step();
+        if (!__builtin_amdgcn_readfirstlane(flag)) return mgs_abort_step(ctrl, step);
       } else {
         double *xs = pbuf + (size_t)(p & 1) * G * k;
         if (tid < k) st_agent(xs + (int64_t)blockIdx.x * k + tid, red[tid]);
         mgs_arrive(bar, (unsigned)(p + 1));
-        if (!mgs_wait(bar, (unsigned)(p + 1), ctrl, &flag, spin_limit)) return abort_step();
+        if (!mgs_wait(bar, (unsigned)(p + 1), ctrl, &flag, fault.spin_limit)) return mgs_abort_step(ctrl, step);
         reduce_rows<kMgsBlock, true>(xs, G, k, red);
         if (tid < k) alpha[tid] = red[tid];
         __syncthreads();
@@ -1142,304 +930,22 @@ __global__ __launch_bounds__(kMgsBlock) void gm_mgsl_kernel(int64_t N, int k, V 
     }
     // chunk 0 of the next pass: its loads must not be waited on by the
     // exchange's drains (vmcnt is in order), so they are issued after the
-    // publish / arrive and travel during the wait
-    const MgslSeg<V> sv2(sub_of(p + 1), e0, N, seg);
-    const V *q2 = next_of(p + 1);
-    if (k == 1) {  // granule all-gather of the block partials
-      unsigned long long *gr = gran + (size_t)(p & 1) * 2 * G;
-      const unsigned tag = ((unsigned)(step + 1) << 12) | (unsigned)(p + 1);
-      if (tid == 0) publish_partial(gr + 2 * blockIdx.x, tag, part1);
+    // publish / arrive and travel during the wait (their descriptors are
+    // made here, ahead of the exchange: made inside `prefetch`, the kernel's
+    // register allocation changes)
+    const MgslSeg<V> sv2(sched.sub_of(p + 1), e0, N, seg);
+    const V *q2 = sched.next_of(p + 1);
+    auto prefetch = [&] {
       if (KC == 0) ld_chunk_sub(sv2, 0, cs[0]);
       ld_chunk(MgslSeg<V>(q2 ? q2 : Vb, e0, N, seg), 0, cn[0]);
-      if (tid < 64) {
-        const bool ok = sweep_partials<false, true>(gr, G, tag, bar, ctrl, alpha, spin_limit);
-        if (tid == 0) flag = ok ? 1 : 0;
-      }
-      __syncthreads();
-      if (!__builtin_amdgcn_readfirstlane(flag)) return abort_step();
+    };
+    if (k == 1) {  // granule all-gather of the block partials
+      if (!mgs_exchange1(gran, step, p, part1, bar, ctrl, alpha, &flag, fault.spin_limit, prefetch))
+        return mgs_abort_step(ctrl, step);
       continue;
     }
-    if (tid < k) st_agent(slot + (int64_t)blockIdx.x * k + tid, red[tid]);
-    mgs_arrive(bar, (unsigned)(p + 1));
-    if (KC == 0) ld_chunk_sub(sv2, 0, cs[0]);
-    ld_chunk(MgslSeg<V>(q2 ? q2 : Vb, e0, N, seg), 0, cn[0]);
-    if (!mgs_wait(bar, (unsigned)(p + 1), ctrl, &flag, spin_limit)) return abort_step();
-    reduce_rows<kMgsBlock, true>(slot, G, k, red);
-    if (tid < k) alpha[tid] = red[tid];
-    __syncthreads();
-  }
-}
-
-// ----------------------- streamed persistent MGS with the two-vector lookahead
-// gm_mgsl_kernel's streaming (w in registers, the basis streamed in chunks of
-// one granule per vector, chunk c + 1 loaded while chunk c is used, chunk 0
-// of the next pass loaded before the exchange) with gm_mgsp2_kernel's groups:
-// pass t streams its two subtrahends (group t) and its two partners (group
-// t + 1) and performs ONE exchange of <V_a', w>, <V_b', w>, <V_b', V_a'>. The
-// first KU granule rows of each partner are kept in LDS for its second read
-// as a subtrahend in the next pass (per-thread storage, no barrier), as the
-// one-vector kernel keeps its partner's. After the last group: the <w, w>
-// exchange and V_{k+1} = w / guard(h[k+1]) from the registers, as there.
-template <typename V, int NV, bool NT>
-__global__ __launch_bounds__(kMgsBlock) void gm_mgsl2_kernel(int64_t N, int k, V *__restrict__ w,
-                                                             const V *__restrict__ Vb, size_t stride, int col,
-                                                             int sweeps, const double *__restrict__ part0, int P0,
-                                                             double *__restrict__ pbuf, double *__restrict__ h,
-                                                             unsigned *bar, unsigned long long *gran, Ctrl *ctrl,
-                                                             int step, int fault_step, V *__restrict__ vnext) {
-  if (halted(ctrl, step)) return;
-  constexpr int W = Vec16<V>::W;
-  constexpr int KEEP = W == 2 ? 9 : 8;  // granule rows kept per partner (two partners: ~147 KiB)
-  constexpr int KU = NV < KEEP ? NV : KEEP;
-  __shared__ __attribute__((aligned(16))) V keep[2][KU][kMgsBlock * W];
-  __shared__ double red[kMgsBlock * W];
-  __shared__ double alpha[2 * kMaxCols];
-  __shared__ double xs[3];
-  __shared__ int flags[3];
-  __shared__ int flag;
-  const int tid = threadIdx.x;
-  const int G = gridDim.x;
-  const bool fault_here = fault_step >= 0 && (fault_step & 0xffff) == step && (int)blockIdx.x == G - 1;
-  const bool fault_final = (fault_step >> 16) == 1;
-  if (fault_here && !fault_final) return;
-  const unsigned spin_limit = fault_step >= 0 ? kSpinLimitFault : kSpinLimit;
-  auto abort_step = [&]() {
-    if (tid == 0) atomicMin(&ctrl->stop_at, step);
-  };
-  const int64_t seg = (int64_t)NV * kMgsBlock * W;
-  const int64_t e0 = (int64_t)blockIdx.x * seg;
-  int colv[W];
-#pragma unroll
-  for (int v = 0; v < W; ++v) colv[v] = (tid * W + v) & (k - 1);
-  typedef BufSeg<V, kMgsBlock> Seg;
-  const Seg ws(w, e0, N, seg);
-  V wr[NV][W];
-#pragma unroll
-  for (int u = 0; u < NV; ++u) ws.template load<W>(u, wr[u]);
-  const int np = sweeps * (col + 1);
-  const int ng = la_groups(np);
-  auto vec_of = [&](int m) -> const V * { return Vb + stride * (size_t)(m % (col + 1)); };
-  typedef V vec_t __attribute__((ext_vector_type(W)));
-  auto keep_ld = [&](int s, int g, V(&o)[W]) {
-    const vec_t t = *reinterpret_cast<const vec_t *>(&keep[s][g][tid * W]);
-#pragma unroll
-    for (int v = 0; v < W; ++v) o[v] = t[v];
-  };
-  auto keep_st = [&](int s, int g, const V(&o)[W]) {
-    vec_t t;
-#pragma unroll
-    for (int v = 0; v < W; ++v) t[v] = o[v];
-    *reinterpret_cast<vec_t *>(&keep[s][g][tid * W]) = t;
-  };
-  // chunk buffers [parity][stream][element]: streams S_a, S_b, T_a, T_b
-  V cb[2][4][W];
-  // chunk c of pass t's streams into cb[par] (the subtrahends only beyond the kept rows)
-  auto ld_chunk = [&](int t, int c, int par) {
-    const int sS = la_size(t, np), sT = la_size(t + 1, np);
-    const int m0 = la_first(t), m1 = la_first(t + 1);
-    if (c >= KU) {
-      Seg(vec_of(m0), e0, N, seg).template load<W, NT ? 2 : 0>(c, cb[par][0]);
-      if (sS == 2) Seg(vec_of(m0 + 1), e0, N, seg).template load<W, NT ? 2 : 0>(c, cb[par][1]);
-    }
-    if (sT >= 1) Seg(vec_of(m1), e0, N, seg).template load<W>(c, cb[par][2]);
-    if (sT == 2) Seg(vec_of(m1 + 1), e0, N, seg).template load<W>(c, cb[par][3]);
-  };
-  {
-    const Seg s0(Vb, e0, N, seg);
-#pragma unroll
-    for (int g = 0; g < KU; ++g) {  // V_0's kept rows
-      V t[W];
-      s0.template load<W>(g, t);
-      keep_st(0, g, t);
-    }
-    ld_chunk(0, 0, 0);
-  }
-  reduce_rows<kMgsBlock, false>(part0, P0, k, red);  // alpha_0 = <V_0, w> from the SpMV's partials
-  if (tid < k) alpha[tid] = red[tid];
-  __syncthreads();
-  for (int t = 0; t < ng; ++t) {
-    const int sS = la_size(t, np), sT = la_size(t + 1, np);
-    const int m0 = la_first(t);
-    if (blockIdx.x == 0 && tid < k) {  // h[j] += alpha_j (arnoldi.py:160-161)
-      for (int i = 0; i < sS; ++i) {
-        const int m = m0 + i, j = m % (col + 1);
-        const V a = (V)alpha[i * k + tid];
-        const V prev = m <= col ? V(0) : (V)h[(int64_t)j * k + tid];
-        h[(int64_t)j * k + tid] = (double)(prev + a);
-      }
-    }
-    V a1[W], a2[W];
-#pragma unroll
-    for (int v = 0; v < W; ++v) {
-      a1[v] = (V)alpha[colv[v]];
-      a2[v] = (V)alpha[k + colv[v]];
-    }
-    double acc[3][W];
-#pragma unroll
-    for (int n = 0; n < 3; ++n)
-#pragma unroll
-      for (int v = 0; v < W; ++v) acc[n][v] = 0.0;
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      const int b = c & 1;
-      __builtin_amdgcn_sched_barrier(0);
-      if (c + 1 < NV) ld_chunk(t, c + 1, b ^ 1);
-      V sa[W], sb[W];
-      if (c < KU) {
-        keep_ld(0, c, sa);
-        if (sS == 2) keep_ld(1, c, sb);
-        if (sT >= 1) keep_st(0, c, cb[b][2]);  // the next pass's subtrahends
-        if (sT == 2) keep_st(1, c, cb[b][3]);
-      } else {
-#pragma unroll
-        for (int v = 0; v < W; ++v) {
-          sa[v] = cb[b][0][v];
-          sb[v] = cb[b][1][v];
-        }
-      }
-#pragma unroll
-      for (int v = 0; v < W; ++v) {
-        wr[c][v] = wr[c][v] - a1[v] * sa[v];
-        if (sS == 2) wr[c][v] = wr[c][v] - a2[v] * sb[v];
-        const double x = (double)wr[c][v];
-        if (sT == 0) {
-          acc[0][v] += dterm(x, x);
-        } else {
-          acc[0][v] += dterm((double)cb[b][2][v], x);
-          if (sT == 2) {
-            acc[1][v] += dterm((double)cb[b][3][v], x);
-            acc[2][v] += dterm((double)cb[b][3][v], (double)cb[b][2][v]);
-          }
-        }
-        asm volatile("" : "+v"(acc[0][v]));  // the accumulation in program order (see gm_mgsl_kernel)
-      }
-    }
-    const int nval = sT == 2 ? 3 : 1;
-    double pv[3] = {0.0, 0.0, 0.0};
-    if (k == 1) {
-      double t3[3];
-#pragma unroll
-      for (int n = 0; n < 3; ++n) {
-        t3[n] = acc[n][0];
-#pragma unroll
-        for (int v = 1; v < W; ++v) t3[n] += acc[n][v];
-      }
-      if (nval == 3) {
-        block_sumn_t0_dpp<3>(t3, red + kMgsBlock);
-      } else {
-        double t1[1] = {t3[0]};
-        block_sumn_t0_dpp<1>(t1, red + kMgsBlock);
-        t3[0] = t1[0];
-      }
-#pragma unroll
-      for (int n = 0; n < 3; ++n) pv[n] = t3[n];
-    }
-    if (t == ng - 1) {
-      double *tot = pbuf + (size_t)6 * G * k;
-      if (vnext == nullptr) {  // <w, w> partials for the QR kernel; w back to HBM
-        if (k == 1) {
-          if (tid == 0) tot[blockIdx.x] = pv[0];
-        } else {
-          __syncthreads();
-#pragma unroll
-          for (int v = 0; v < W; ++v) red[tid * W + v] = acc[0][v];
-          block_tree_reduce(red, kMgsBlock * W, k);
-          if (tid < k) tot[(int64_t)blockIdx.x * k + tid] = red[tid];
-        }
-#pragma unroll
-        for (int u = 0; u < NV; ++u) ws.template store<W>(u, wr[u]);
-        return;
-      }
-      // the <w, w> exchange, h[k+1] and its guard as the QR kernel forms
-      // them, and V_{k+1} = w / guard(h[k+1]) from the registers
-      // (arnoldi.py:185,191-196); the QR kernel reads the sum as one row
-      if (fault_here) return;  // KRY_MGS_FAULT_FINAL: never joins the normalising exchange
-      if (k == 1) {
-        unsigned long long *gr = gran + (size_t)(t & 1) * 3 * 2 * G;
-        const unsigned tag = ((unsigned)(step + 1) << 12) | (unsigned)(t + 1);
-        if (tid == 0) publish_partials_n<1>(gr, G, tag, pv);
-        if (tid < 64) {
-          const bool ok = sweep_partials_n<1>(gr, G, tag, bar, ctrl, xs, spin_limit);
-          if (tid == 0) {
-            flag = ok ? 1 : 0;
-            alpha[0] = xs[0];
-          }
-        }
-        __syncthreads();
-        if (!__builtin_amdgcn_readfirstlane(flag)) return abort_step();
-      } else {
-        double *xsl = pbuf + (size_t)(t & 1) * 3 * G * k;
-        __syncthreads();
-#pragma unroll
-        for (int v = 0; v < W; ++v) red[tid * W + v] = acc[0][v];
-        block_tree_reduce(red, kMgsBlock * W, k);
-        if (tid < k) st_agent(xsl + (int64_t)blockIdx.x * k + tid, red[tid]);
-        mgs_arrive(bar, (unsigned)(t + 1));
-        if (!mgs_wait(bar, (unsigned)(t + 1), ctrl, &flag, spin_limit)) return abort_step();
-        reduce_rows<kMgsBlock, true>(xsl, G, k, red);
-        if (tid < k) alpha[tid] = red[tid];
-        __syncthreads();
-      }
-      if (blockIdx.x == 0 && tid < k) tot[tid] = alpha[tid];
-      V hs[W];
-#pragma unroll
-      for (int v = 0; v < W; ++v) hs[v] = safe<V>(sqrt((V)alpha[colv[v]]));
-      const Seg vs(vnext, e0, N, seg);
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        V o[W];
-#pragma unroll
-        for (int v = 0; v < W; ++v) o[v] = wr[u][v] / hs[v];
-        vs.template store<W>(u, o);
-      }
-      return;
-    }
-    if (k == 1) {  // granule all-gather of the block partials, one wave per value
-      unsigned long long *gr = gran + (size_t)(t & 1) * 3 * 2 * G;
-      const unsigned tag = ((unsigned)(step + 1) << 12) | (unsigned)(t + 1);
-      if (tid == 0) {
-        if (nval == 3) publish_partials_n<3>(gr, G, tag, pv);
-        else publish_partials_n<1>(gr, G, tag, pv);
-      }
-      ld_chunk(t + 1, 0, 0);  // chunk 0 of the next pass travels during the wait
-      if (tid < 64 * nval) {
-        const int v = tid >> 6;
-        const bool ok = sweep_partials_n<1>(gr + (size_t)2 * v * G, G, tag, bar, ctrl, xs + v, spin_limit);
-        if ((tid & 63) == 0) flags[v] = ok ? 1 : 0;
-      }
-      __syncthreads();
-      if (!(flags[0] && (nval == 1 || (flags[1] && flags[2])))) return abort_step();
-      if (tid == 0) {
-        const V aa = (V)xs[0];
-        alpha[0] = xs[0];
-        if (nval == 3) alpha[1] = xs[1] - (double)aa * xs[2];
-      }
-      __syncthreads();
-      continue;
-    }
-    double *slot = pbuf + (size_t)(t & 1) * 3 * G * k;
-    for (int n = 0; n < nval; ++n) {
-      __syncthreads();
-#pragma unroll
-      for (int v = 0; v < W; ++v) red[tid * W + v] = acc[n][v];
-      block_tree_reduce(red, kMgsBlock * W, k);
-      if (tid < k) st_agent(slot + ((int64_t)n * G + blockIdx.x) * k + tid, red[tid]);
-    }
-    mgs_arrive(bar, (unsigned)(t + 1));
-    ld_chunk(t + 1, 0, 0);
-    if (!mgs_wait(bar, (unsigned)(t + 1), ctrl, &flag, spin_limit)) return abort_step();
-    double xv[3] = {0.0, 0.0, 0.0};
-    for (int n = 0; n < nval; ++n) {
-      reduce_rows<kMgsBlock, true>(slot + (int64_t)n * G * k, G, k, red);
-      if (tid < k) xv[n] = red[tid];
-      __syncthreads();
-    }
-    if (tid < k) {
-      const V aa = (V)xv[0];
-      alpha[tid] = xv[0];
-      if (nval == 3) alpha[k + tid] = xv[1] - (double)aa * xv[2];
-    }
-    __syncthreads();
+    if (!mgs_exchange_k(slot, k, p, bar, ctrl, red, alpha, &flag, fault.spin_limit, prefetch))
+      return mgs_abort_step(ctrl, step);
   }
 }
 
@@ -2072,103 +1578,110 @@ void hh_run_impl(kry_gmres *s, int max_steps) {
   }
 }
 
-// Launch the persistent MGS kernel for this Arnoldi step if w fits the
-// registers of one resident 512-thread block per CU; false = not eligible
-// (decided once per solver: s->mgsp_E = 0 no, else elements per thread).
+// ------------------------------ persistent MGS: the kernel choice and launch
 // Up to 16 doubles per thread w and the two basis vectors stay in registers
-// (gm_mgsp_kernel); up to 80 only w does and the basis is streamed
-// (gm_mgsl_kernel, n = 10 M at one column).
+// (gm_mgsp_kernel, gm_mgsp3_kernel); up to 80 only w does and the basis is
+// streamed (gm_mgsl_kernel, n = 10 M at one column).
 // granules per streamed chunk: 4 (2 from NV = 32 on, where 4 would spill)
 template <int NV>
 constexpr int mgsl_u() {
   return NV >= 32 ? 2 : 4;
 }
-// The two-vector lookahead MGS (gm_mgsp2_kernel / gm_mgsl2_kernel) is
-// opt-in: KRY_MGS_LOOKAHEAD=1 (register-resident kernel), KRY_MGSL_LOOKAHEAD=1
-// (streamed kernel). Both measured slower than the one-exchange-per-pass
-// forms on one box, alternating processes (profiles/r06_mgs_lookahead_ab.txt):
-// cfg3 0.100 against 0.082 ms per step, the metric 0.405 against 0.356 ms
-// (its two partners share the LDS room one partner had, so it re-reads more
-// of the basis).
-inline bool mgs_lookahead() {
-  static const bool on = [] {
-    const char *e = getenv("KRY_MGS_LOOKAHEAD");
-    return e && atoi(e) == 1;
-  }();
-  return on;
+
+// One candidate: the kernel launched, on ceil(N / (512 E)) blocks.
+struct MgspRow {
+  const void *kern;
+  int E;          // elements of w per thread
+  bool streamed;  // a gm_mgsl_kernel: its last parameter is V_{col+1}, which it writes
+};
+template <typename V, int E>
+MgspRow mgsp_row(bool pf2) {
+  return {pf2 ? reinterpret_cast<const void *>(&gm_mgsp3_kernel<V, E>)
+              : reinterpret_cast<const void *>(&gm_mgsp_kernel<V, E>),
+          E, false};
 }
-// the register-resident MGS at k = 1 with the partner copied two passes
-// ahead into LDS (gm_mgsp3_kernel): default; KRY_MGS_PF2=0 restores
-// gm_mgsp_kernel (bitwise the same results). cfg3 GMRES(30): MGS 0.084 ->
-// 0.079 ms per step, 2,867 -> 2,920 it/s, same box, alternating processes
-// (profiles/r06_mgs_pf2_ab.txt)
-inline bool mgs_pf2() {
-  const char *e = getenv("KRY_MGS_PF2");  // read per launch: the tests switch it within one process
-  return !(e && atoi(e) == 0);
+template <typename V, int NV>
+MgspRow mgsl_row(bool nt, bool u4) {
+  constexpr int U = mgsl_u<NV>();
+  const void *kern = nt ? reinterpret_cast<const void *>(&gm_mgsl_kernel<V, NV, U, true>)
+                        : reinterpret_cast<const void *>(&gm_mgsl_kernel<V, NV, U, false>);
+  if constexpr (sizeof(V) == 8 && NV >= 32) {
+    if (nt && u4) kern = reinterpret_cast<const void *>(&gm_mgsl_kernel<V, NV, 4, true>);
+  }
+  return {kern, NV * Vec16<V>::W, true};
 }
-inline bool mgsl_lookahead() {
-  static const bool on = [] {
-    const char *e = getenv("KRY_MGSL_LOOKAHEAD");
-    return e && atoi(e) == 1;
-  }();
-  return on;
+
+// The candidates for k columns of V, in the order they are tried. Every
+// switch is read here, once per solver:
+//   KRY_MGS_PERSIST  0: none; 1: the register-resident kernels only
+//   KRY_MGS_PF2      0: gm_mgsp_kernel at k = 1 too. By default one column
+//                    runs gm_mgsp3_kernel (the partner copied two passes
+//                    ahead into LDS, bitwise the same results): cfg3
+//                    GMRES(30) MGS 0.084 -> 0.079 ms per step, 2,867 -> 2,920
+//                    it/s, same box, alternating processes
+//                    (profiles/r06_mgs_pf2_ab.txt)
+//   KRY_MGSL_NT      tuning override: the streamed kernel's subtrahend loads
+//                    nontemporal (1, default) or not (0)
+//   KRY_MGSL_U       tuning override: 4 granules per streamed chunk at
+//                    NV >= 32 (double, nontemporal)
+template <typename V>
+std::vector<MgspRow> mgsp_rows(int k) {
+  auto env = [](const char *name, int unset) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : unset;
+  };
+  std::vector<MgspRow> rows;
+  const int persist = env("KRY_MGS_PERSIST", -1);
+  if (persist == 0) return rows;
+  const bool pf2 = k == 1 && env("KRY_MGS_PF2", 1) != 0;
+  rows.push_back(mgsp_row<V, 8>(pf2));
+  rows.push_back(mgsp_row<V, 16>(pf2));
+  // (E = 32 doubles per thread would spill: float only)
+  if constexpr (sizeof(V) == 4) rows.push_back(mgsp_row<V, 32>(pf2));
+  if (persist == 1) return rows;
+  const bool nt = env("KRY_MGSL_NT", 1) != 0;
+  const bool u4 = env("KRY_MGSL_U", 0) == 4;
+  rows.push_back(mgsl_row<V, 12>(nt, u4));
+  rows.push_back(mgsl_row<V, 16>(nt, u4));
+  rows.push_back(mgsl_row<V, 24>(nt, u4));
+  rows.push_back(mgsl_row<V, 32>(nt, u4));
+  rows.push_back(mgsl_row<V, 40>(nt, u4));
+  return rows;
 }
+
+// Launch the persistent MGS kernel for this Arnoldi step; false = not
+// eligible. The kernel is chosen at the solver's first step (s->mgsp_E = 0:
+// none, else the elements per thread of s->mgsp_kern): the first candidate
+// whose grid has one block per CU at most and which the occupancy query, on
+// the very kernel launched, finds resident.
 template <typename V>
 bool mgsp_launch(kry_gmres *s, V *w, const double *pin, int Pin, int col, int step) {
-  const int64_t N = s->n * (int64_t)s->k;
-  constexpr int W = Vec16<V>::W;
+  int64_t N = s->n * (int64_t)s->k;
+  auto grid_of = [&](int E) { return (N + (int64_t)kMgsBlock * E - 1) / ((int64_t)kMgsBlock * E); };
   if (s->mgsp_E < 0) {
     s->mgsp_E = 0;
-    s->mgsp_large = false;
-    const char *e = getenv("KRY_MGS_PERSIST");
-    if (!(e && atoi(e) == 0)) {
-      int dev = 0, ncu = 0;
-      KRY_HIP(hipGetDevice(&dev));
-      KRY_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-      auto fits = [&](auto kern, int E) {
-        const int64_t G = (N + (int64_t)kMgsBlock * E - 1) / ((int64_t)kMgsBlock * E);
-        int per_cu = 0;
-        KRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kMgsBlock, 0));
-        // one block per CU: VGPR-bound residency (<= 256 VGPRs at 2 waves
-        // per SIMD), far from the SGPR band where the answer runs high
-        return G <= ncu && G <= 256 && per_cu >= 1 && (int64_t)s->sweeps * (s->maxiter + 1) < 4095;
-      };
-      // (E = 32 doubles per thread would spill: float only)
-      const bool pf2 = !mgs_lookahead() && s->k == 1 && mgs_pf2();
-      if (pf2 ? fits(gm_mgsp3_kernel<V, 8>, 8)
-              : (mgs_lookahead() ? fits(gm_mgsp2_kernel<V, 8>, 8) : fits(gm_mgsp_kernel<V, 8>, 8)))
-        s->mgsp_E = 8;
-      else if (pf2 ? fits(gm_mgsp3_kernel<V, 16>, 16)
-                   : (mgs_lookahead() ? fits(gm_mgsp2_kernel<V, 16>, 16) : fits(gm_mgsp_kernel<V, 16>, 16)))
-        s->mgsp_E = 16;
-      else if constexpr (sizeof(V) == 4) {
-        if (mgs_lookahead() ? fits(gm_mgsp2_kernel<V, 32>, 32) : fits(gm_mgsp_kernel<V, 32>, 32)) s->mgsp_E = 32;
-      }
-      if (s->mgsp_E == 0 && !(e && atoi(e) == 1)) {  // KRY_MGS_PERSIST=1: the register-resident kernel only
-        s->mgsp_large = true;
-        const bool la = mgsl_lookahead();
-        if (la ? fits(gm_mgsl2_kernel<V, 12, true>, 12 * W) : fits(gm_mgsl_kernel<V, 12, mgsl_u<12>(), true>, 12 * W))
-          s->mgsp_E = 12 * W;
-        else if (la ? fits(gm_mgsl2_kernel<V, 16, true>, 16 * W)
-                    : fits(gm_mgsl_kernel<V, 16, mgsl_u<16>(), true>, 16 * W))
-          s->mgsp_E = 16 * W;
-        else if (la ? fits(gm_mgsl2_kernel<V, 24, true>, 24 * W)
-                    : fits(gm_mgsl_kernel<V, 24, mgsl_u<24>(), true>, 24 * W))
-          s->mgsp_E = 24 * W;
-        else if (la ? fits(gm_mgsl2_kernel<V, 32, true>, 32 * W)
-                    : fits(gm_mgsl_kernel<V, 32, mgsl_u<32>(), true>, 32 * W))
-          s->mgsp_E = 32 * W;
-        else if (la ? fits(gm_mgsl2_kernel<V, 40, true>, 40 * W)
-                    : fits(gm_mgsl_kernel<V, 40, mgsl_u<40>(), true>, 40 * W))
-          s->mgsp_E = 40 * W;
-        else s->mgsp_large = false;
-      }
+    int dev = 0, ncu = 0;
+    KRY_HIP(hipGetDevice(&dev));
+    KRY_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    // (the pass number has 12 bits of the k = 1 exchange's tag)
+    const bool tags = (int64_t)s->sweeps * (s->maxiter + 1) < 4095;
+    for (const MgspRow &r : mgsp_rows<V>(s->k)) {
+      const int64_t G = grid_of(r.E);
+      if (!tags || G > ncu || G > 256) continue;
+      // one block per CU: VGPR-bound residency (<= 256 VGPRs at 2 waves per
+      // SIMD), far from the SGPR band where the answer runs high
+      int per_cu = 0;
+      KRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r.kern, kMgsBlock, 0));
+      if (per_cu < 1) continue;
+      s->mgsp_kern = r.kern;
+      s->mgsp_E = r.E;
+      s->mgsp_streamed = r.streamed;
+      break;
     }
   }
   if (s->mgsp_E == 0) return false;
   hipStream_t st = s->ctx->stream;
-  const int E = s->mgsp_E;
-  const int G = (int)((N + (int64_t)kMgsBlock * E - 1) / ((int64_t)kMgsBlock * E));
+  const int G = (int)grid_of(s->mgsp_E);
   if (step == 0) KRY_HIP(hipMemsetAsync(s->bar, 0, bar_bytes(s->chunk_cap), st));
   unsigned *bar = s->bar + (size_t)step * kBarWords;
   unsigned long long *gran = reinterpret_cast<unsigned long long *>(s->bar + (size_t)s->chunk_cap * kBarWords);
@@ -2176,7 +1689,7 @@ bool mgsp_launch(kry_gmres *s, V *w, const double *pin, int Pin, int col, int st
   ProfScope ps(s->ctx, PROF_MGS);
   const char *fe = getenv("KRY_MGS_FAULT");  // fault injection (tests): chunk step at which a block drops out
   const char *ff = getenv("KRY_MGS_FAULT_FINAL");  // ... at the streamed kernel's final exchange instead
-  const int fault_step = fe ? (atoi(fe) | ((ff && atoi(ff) == 1) ? (1 << 16) : 0)) : -1;
+  int fault_step = fe ? (atoi(fe) | ((ff && atoi(ff) == 1) ? (1 << 16) : 0)) : -1;
   // KRY_MGS_TRACE: per-block phase sums of the register-resident kernels,
   // accumulated over the solver's launches and printed at its destroy
   static const bool trace = getenv("KRY_MGS_TRACE") != nullptr;
@@ -2185,79 +1698,21 @@ bool mgsp_launch(kry_gmres *s, V *w, const double *pin, int Pin, int col, int st
     KRY_HIP(hipMemsetAsync(s->mgs_tbuf, 0, 256 * 4 * 8, st));
   }
   if (trace) {
-    s->mgs_tpasses += (int64_t)(mgs_lookahead() ? (1 + s->sweeps * (col + 1) / 2) : s->sweeps * (col + 1));
+    s->mgs_tpasses += (int64_t)s->sweeps * (col + 1);
     s->mgs_tgrid = G;
   }
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(G), dim3(kMgsBlock), 0, st, N, s->k, w, (const V *)s->V, s->vstride, col, s->sweeps,
-                       pin, Pin, pbuf, s->h, bar, gran, s->ctrl, step, fault_step, s->mgs_tbuf);
-  };
-  // the streamed kernel also normalises: V_{col+1} = w / guard(h[col+1])
-  V *vnext = basis<V>(s->V, s->vstride, col + 1);
-  auto gol = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(G), dim3(kMgsBlock), 0, st, N, s->k, w, (const V *)s->V, s->vstride, col, s->sweeps,
-                       pin, Pin, pbuf, s->h, bar, gran, s->ctrl, step, fault_step, vnext);
-  };
-  s->mgsp_norm = s->mgsp_large;
-  static const bool mgsl_nt = [] {
-    const char *e = getenv("KRY_MGSL_NT");  // tuning override: subtrahend loads nontemporal (1) or not (0)
-    return e ? atoi(e) != 0 : true;
-  }();
-  static const int mgsl_u_env = [] {
-    const char *e = getenv("KRY_MGSL_U");  // tuning override: granules per streamed chunk at NV >= 32 (2 or 4)
-    return e ? atoi(e) : 0;
-  }();
-  bool u4 = false;
-  if constexpr (sizeof(V) == 8) u4 = s->mgsp_large && mgsl_nt && mgsl_u_env == 4 && E / W >= 32;
-  const bool la = s->mgsp_large ? mgsl_lookahead() : mgs_lookahead();
-  if (s->mgsp_large && la) {
-    switch (E / W) {
-      case 12: gol(gm_mgsl2_kernel<V, 12, true>); break;
-      case 16: gol(gm_mgsl2_kernel<V, 16, true>); break;
-      case 24: gol(gm_mgsl2_kernel<V, 24, true>); break;
-      case 32: gol(gm_mgsl2_kernel<V, 32, true>); break;
-      default: gol(gm_mgsl2_kernel<V, 40, true>); break;
-    }
-  } else if (u4) {
-    if constexpr (sizeof(V) == 8) {
-      if (E / W == 32) gol(gm_mgsl_kernel<V, 32, 4, true>);
-      else gol(gm_mgsl_kernel<V, 40, 4, true>);
-    }
-  } else if (s->mgsp_large && mgsl_nt) {
-    switch (E / W) {
-      case 12: gol(gm_mgsl_kernel<V, 12, mgsl_u<12>(), true>); break;
-      case 16: gol(gm_mgsl_kernel<V, 16, mgsl_u<16>(), true>); break;
-      case 24: gol(gm_mgsl_kernel<V, 24, mgsl_u<24>(), true>); break;
-      case 32: gol(gm_mgsl_kernel<V, 32, mgsl_u<32>(), true>); break;
-      default: gol(gm_mgsl_kernel<V, 40, mgsl_u<40>(), true>); break;
-    }
-  } else if (s->mgsp_large) {
-    switch (E / W) {
-      case 12: gol(gm_mgsl_kernel<V, 12, mgsl_u<12>(), false>); break;
-      case 16: gol(gm_mgsl_kernel<V, 16, mgsl_u<16>(), false>); break;
-      case 24: gol(gm_mgsl_kernel<V, 24, mgsl_u<24>(), false>); break;
-      case 32: gol(gm_mgsl_kernel<V, 32, mgsl_u<32>(), false>); break;
-      default: gol(gm_mgsl_kernel<V, 40, mgsl_u<40>(), false>); break;
-    }
-  } else if (!la && s->k == 1 && mgs_pf2()) {
-    if (E == 8) go(gm_mgsp3_kernel<V, 8>);
-    else if (E == 16) go(gm_mgsp3_kernel<V, 16>);
-    else if constexpr (sizeof(V) == 4) go(gm_mgsp3_kernel<V, 32>);
-  } else if (la) {
-    if (E == 8) go(gm_mgsp2_kernel<V, 8>);
-    else if (E == 16) go(gm_mgsp2_kernel<V, 16>);
-    else if constexpr (sizeof(V) == 4) go(gm_mgsp2_kernel<V, 32>);
-  } else if (E == 8) {
-    go(gm_mgsp_kernel<V, 8>);
-  } else if (E == 16) {
-    go(gm_mgsp_kernel<V, 16>);
-  } else if constexpr (sizeof(V) == 4) {
-    go(gm_mgsp_kernel<V, 32>);
-  }
-  KRY_HIP(hipGetLastError());
+  // The kernels share their parameter list up to the last pointer: the trace
+  // buffer, or for the streamed kernel, which also normalises, V_{col+1} =
+  // w / guard(h[col+1]).
+  const V *Vb = static_cast<const V *>(s->V);
+  void *last = s->mgsp_streamed ? static_cast<void *>(basis<V>(s->V, s->vstride, col + 1))
+                                : static_cast<void *>(s->mgs_tbuf);
+  void *args[] = {&N,  &s->k, &w,     &Vb,  &s->vstride, &col,  &s->sweeps, &pin,        &Pin,
+                  &pbuf, &s->h, &bar, &gran, &s->ctrl,   &step, &fault_step, &last};
+  KRY_HIP(hipLaunchKernel(s->mgsp_kern, dim3(G), dim3(kMgsBlock), args, 0, st));
+  s->mgsp_norm = s->mgsp_streamed;
   s->mgsp_grid = s->mgsp_norm ? 1 : G;  // normalising: the exchanged sum, one row
-  // the <w, w> partials: slot 2 of the one-value kernels, slot 6 of the lookahead's three-value parities
-  s->mgsp_out = pbuf + (size_t)(la ? 6 : 2) * G * s->k;
+  s->mgsp_out = pbuf + (size_t)2 * G * s->k;  // the <w, w> partials
   return true;
 }
 

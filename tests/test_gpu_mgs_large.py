@@ -110,3 +110,59 @@ def test_mgs_partner_two_passes_ahead_is_bitwise(monkeypatch):
         _, i0 = krylov_amd.gmres(krylov_amd.CsrOperator(R), b, ortho=ortho, maxiter=30, tol=0.0)
         np.testing.assert_array_equal(np.asarray(i1.resnorms).view(np.uint8), np.asarray(i0.resnorms).view(np.uint8))
         np.testing.assert_array_equal(np.asarray(i1.xk).view(np.uint8), np.asarray(i0.xk).view(np.uint8))
+
+
+@pytest.mark.parametrize("n", [123_457, 2_100_003])
+def test_mgs_partner_two_passes_ahead_is_bitwise_float32(n, monkeypatch):
+    """The same in float32 (matrix and right-hand side), where the
+    register-resident kernels go up to 32 elements per thread: n = 123,457 is
+    ragged at 8 per thread; n = 2,100,003 is past the 2,097,152 that 16 per
+    thread cover, so it runs 32 per thread on 129 blocks, the last one holding
+    2,851 of its 16,384 elements (3 entries per row keep the matrix quick to
+    build)."""
+    import krylov_amd
+    from krylov_amd import problems
+
+    R = problems.random_nonsym(n, per_row=3).astype(np.float32)
+    b = np.random.default_rng(3).standard_normal(n).astype(np.float32)
+    monkeypatch.setenv("KRY_MGS_PF2", "1")
+    A1 = krylov_amd.CsrOperator(R)
+    assert _state_path(A1, b, 1) == (True, 0)
+    _, i1 = krylov_amd.gmres(A1, b, maxiter=8, tol=0.0)
+    monkeypatch.setenv("KRY_MGS_PF2", "0")
+    A0 = krylov_amd.CsrOperator(R)
+    assert _state_path(A0, b, 1) == (True, 0)
+    _, i0 = krylov_amd.gmres(A0, b, maxiter=8, tol=0.0)
+    assert i1.xk.dtype == np.float32 and i1.numsteps == i0.numsteps == 8
+    np.testing.assert_array_equal(np.asarray(i1.resnorms).view(np.uint8), np.asarray(i0.resnorms).view(np.uint8))
+    np.testing.assert_array_equal(np.asarray(i1.xk).view(np.uint8), np.asarray(i0.xk).view(np.uint8))
+
+
+@pytest.mark.parametrize("m", [1024, 1025, 1448, 1449])
+def test_persistent_mgs_selection_boundaries(m, monkeypatch):
+    """The sizes at which the kernel choice changes (float64, one column, 256
+    blocks of 512 threads at most): m = 1024, n = 1,048,576, the last size at
+    8 elements per thread, a full grid; m = 1025, the first at 16; m = 1448,
+    n = 2,096,704, the last register-resident size, its last block ragged;
+    m = 1449, n = 2,099,601, the first streamed size (12 granules). Each
+    against the launch-per-pass path, to the tolerances of
+    test_streamed_mgs_matches_launch_per_pass_and_oracle."""
+    import krylov_amd
+    from krylov_amd import problems
+
+    P = problems.poisson2d(m)
+    assert P.shape[0] == m * m
+    b = np.random.default_rng(11).standard_normal(P.shape[0])
+    A = krylov_amd.CsrOperator(P)
+    assert _state_path(A, b, 1) == (True, 0)
+    _, got = krylov_amd.gmres(A, b, maxiter=6, tol=0.0)
+    monkeypatch.setenv("KRY_MGS_PERSIST", "0")
+    A0 = krylov_amd.CsrOperator(P)
+    assert _state_path(A0, b, 1) == (False, 0)
+    _, lpp = krylov_amd.gmres(A0, b, maxiter=6, tol=0.0)
+    assert got.numsteps == lpp.numsteps == 6
+    g, l = np.asarray(got.resnorms), np.asarray(lpp.resnorms)
+    print(f"m={m}: max rel resnorm diff {np.max(np.abs(g - l) / np.abs(l)):.3e}, "
+          f"max |dx| / max|x| {np.max(np.abs(got.xk - lpp.xk)) / np.abs(lpp.xk).max():.3e}")
+    np.testing.assert_allclose(g, l, rtol=1e-12)
+    np.testing.assert_allclose(got.xk, lpp.xk, rtol=0, atol=1e-11 * np.abs(lpp.xk).max())
