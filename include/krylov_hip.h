@@ -121,7 +121,10 @@ int kry_csr_permute(kry_ctx *ctx, const kry_csr *A, const kry_vec *src, kry_vec 
 /* Byte comparison of two operators' SELL-64 and diagonal-offset images and
  * their sizes (kry_version() >= 104; tests: kry_csr_create builds those images
  * on the device for int32 CSR, KRY_DEVICE_BUILD=0 on the host, and the two
- * must be identical): out[0] = number of differing items, out[1] = bitmask. */
+ * must be identical): out[0] = number of differing items, out[1] = bitmask.
+ * From kry_version() 107 bits 23, 24 and 25 cover the uniform slot columns of
+ * the diagonal-offset image (their count, flags and values); the earlier bits
+ * keep their meaning. */
 int kry_csr_compare(const kry_csr *A, const kry_csr *B, int64_t *out);
 /* kry_spmv with x and y already in the operator's numbering (kry_csr_permute);
  * the same as kry_spmv for an operator that is not renumbered. */
@@ -162,6 +165,19 @@ int kry_csr_layout(int64_t n, const void *indptr, int itype, int64_t *nslices,
  * that offset). Call once with null arrays to size them. */
 int kry_dia_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int64_t *info,
                  int32_t *widths, int32_t *offsets, uint64_t *masks);
+/* Host-only (kry_version() >= 107): the uniform slot columns of that image. A
+ * slot column is uniform when the stored values of all its present rows (the
+ * mask bits; holes take no part) have one bit pattern (-0.0 differs from
+ * +0.0, NaNs compare by payload, a single present row is uniform). The
+ * single-RHS SpMV takes such a column's value from its descriptor and does
+ * not read its 128 stored values; the result stays bitwise csr_matvec.
+ * KRY_DIA_UNIFORM=0 in the environment at kry_csr_create flags no column
+ * (this plan ignores the variable). `data` holds nnz values of `dtype`.
+ * info[0..2] = built (0/1), slot columns (slots / 128), uniform ones; when
+ * built and the arrays are non-null: flags[slots / 128] (0/1) and
+ * values[slots / 128] in `dtype` (0 where not flagged). */
+int kry_dia_uniform_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data, int dtype,
+                         int itype, int64_t *info, int32_t *flags, void *values);
 /* Host-only view of the paired-row SELL-128 plan (no device needed; the
  * image kry_csr_create builds for a general matrix, kry_version() >= 102):
  * info[0..3] = built (0 = refused: a slot column spans more than 65534
@@ -202,7 +218,11 @@ int kry_cb_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices,
  * serves single-RHS SpMVs), its slot count, renumbered (1 when the images hold
  * the reverse Cuthill-McKee renumbering P A P^T) and the renumbering's BFS
  * level count. */
-#define KRY_CSR_INFO_LEN 13
+/* then (kry_version() >= 107) the number of uniform slot columns of the
+ * diagonal-offset image (0 with KRY_DIA_UNIFORM=0) and the bytes of matrix
+ * values the single-RHS kernel still streams per SpMV: (slot columns -
+ * uniform ones) * 128 * the value size. */
+#define KRY_CSR_INFO_LEN 15
 int kry_csr_info_n(const kry_csr *A, int64_t *info, int32_t len);
 /* The version-100 form: info[0..4] only (`info` holds 5 values). */
 int kry_csr_info(const kry_csr *A, int64_t *info);

@@ -75,6 +75,7 @@ _SIGNATURES = {
     "kry_rcm_device": [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _ip64, _vp],
     "kry_csr_layout": [_i64, _vp, _int, _ip64, _ip64, _ip64],
     "kry_dia_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp, _vp, _vp],
+    "kry_dia_uniform_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _int, _int, _ip64, _vp, _vp],
     "kry_pair_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp, _vp, _vp],
     "kry_cb_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp],
     "kry_csr_info": [_vp, _ip64],
@@ -264,6 +265,27 @@ def dia_plan(indptr, indices):
                            ptr(offsets), ptr(masks)))
     return {"slices": int(info[1]), "slots": int(info[2]), "max_width": int(info[3]), "widths": widths,
             "offsets": offsets, "masks": masks}
+
+
+def dia_uniform_plan(indptr, indices, data):
+    """Host-only view of the diagonal-offset image's uniform slot columns
+    (kry_dia_uniform_plan): None if the image would not be built, else
+    {"cols", "uniform", "flags", "values"} (values in data's dtype)."""
+    indptr = np.ascontiguousarray(indptr)
+    indices = np.ascontiguousarray(indices, dtype=indptr.dtype)
+    data = np.ascontiguousarray(data)
+    n, nnz = indptr.shape[0] - 1, indices.shape[0]
+    assert data.shape[0] == nnz
+    info = np.zeros(3, dtype=np.int64)
+    ip64 = info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    args = (n, nnz, ptr(indptr), ptr(indices), ptr(data), dtype_code(data.dtype), itype_code(indptr.dtype), ip64)
+    check(lib.kry_dia_uniform_plan(*args, None, None))
+    if not info[0]:
+        return None
+    flags = np.zeros(int(info[1]), dtype=np.int32)
+    values = np.zeros(int(info[1]), dtype=data.dtype)
+    check(lib.kry_dia_uniform_plan(*args, ptr(flags), ptr(values)))
+    return {"cols": int(info[1]), "uniform": int(info[2]), "flags": flags, "values": values}
 
 
 def pair_plan(indptr, indices):

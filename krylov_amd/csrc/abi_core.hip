@@ -441,8 +441,10 @@ extern "C" {
 // version-100 five values. 102: kry_csr_info_n reports the paired-row image.
 // 103: the per-step allreduces of the sharded solvers carry a fault count
 // (CG total_k + 1, GMRES / MINRES total_k + 2 values); kry_cg_defer_info,
-// kry_gmres_xk_device.
-int kry_version(void) { return 106; }
+// kry_gmres_xk_device. 107: uniform slot columns of the diagonal-offset image
+// (kry_csr_info_n: two more values; kry_dia_uniform_plan; kry_csr_compare:
+// bits 23-25).
+int kry_version(void) { return 107; }
 
 #ifndef KRY_BUILD_ID
 #define KRY_BUILD_ID "unknown"
@@ -523,7 +525,10 @@ int kry_csr_info_n(const kry_csr *A, int64_t *info, int32_t len) {
   const int64_t all[KRY_CSR_INFO_LEN] = {A->nslices,   A->nslots,    A->nirregular,        A->compact ? 1 : 0,
                                          A->cb_nb,      A->dia ? 1 : 0, A->dia_nslots,     A->sp ? 1 : 0,
                                          A->sp_nslots,  A->rs ? 1 : 0, A->rs_nslots,     A->renumbered ? 1 : 0,
-                                         A->rcm_levels};
+                                         A->rcm_levels, A->dia ? A->dia_nuniform : 0,
+                                         A->dia ? (A->dia_nslots / kDiaSlice - A->dia_nuniform) * kDiaSlice *
+                                                      (int64_t)dsize(A->dtype)
+                                                : 0};
   for (int i = 0; i < len && i < KRY_CSR_INFO_LEN; ++i) info[i] = all[i];
   KRY_API_END
 }
@@ -676,8 +681,9 @@ void csr_upload(kry_csr *A, const I *ip, const I *ix, const MV *dv, const std::v
   const char *denv = getenv("KRY_SPMV_DIA");
   if (dres != 2 && !(denv && atoi(denv) == 0)) {
     DiaHost<MV> dh;
-    if (dia_build(n, ip, ix, dv, A->nslots, dh)) {
+    if (dia_build(n, ip, ix, dv, A->nslots, dh, !env_off("KRY_DIA_UNIFORM"))) {
       A->dia = true;
+      A->dia_nuniform = dh.nuniform;
       A->dia_nslices = (int64_t)dh.width.size();
       A->dia_nslots = dh.sptr.back();
       A->dia_max_width = dh.max_width;
@@ -686,11 +692,15 @@ void csr_upload(kry_csr *A, const I *ip, const I *ix, const MV *dv, const std::v
       A->dia_off = dev_alloc(dh.off.size() * 4);
       A->dia_mask = dev_alloc(dh.mask.size() * 8);
       A->dia_val = dev_alloc(dh.val.size() * sizeof(MV));
+      A->dia_uflag = dev_alloc(dh.uflag.size() * 4);
+      A->dia_uval = dev_alloc(dh.uval.size() * sizeof(MV));
       KRY_HIP(hipMemcpyAsync(A->dia_sptr, dh.sptr.data(), dh.sptr.size() * 8, hipMemcpyHostToDevice, st));
       KRY_HIP(hipMemcpyAsync(A->dia_width, dh.width.data(), dh.width.size() * 4, hipMemcpyHostToDevice, st));
       KRY_HIP(hipMemcpyAsync(A->dia_off, dh.off.data(), dh.off.size() * 4, hipMemcpyHostToDevice, st));
       KRY_HIP(hipMemcpyAsync(A->dia_mask, dh.mask.data(), dh.mask.size() * 8, hipMemcpyHostToDevice, st));
       KRY_HIP(hipMemcpyAsync(A->dia_val, dh.val.data(), dh.val.size() * sizeof(MV), hipMemcpyHostToDevice, st));
+      KRY_HIP(hipMemcpyAsync(A->dia_uflag, dh.uflag.data(), dh.uflag.size() * 4, hipMemcpyHostToDevice, st));
+      KRY_HIP(hipMemcpyAsync(A->dia_uval, dh.uval.data(), dh.uval.size() * sizeof(MV), hipMemcpyHostToDevice, st));
       KRY_HIP(hipStreamSynchronize(st));
       release_later(dh.val);
     }
@@ -790,7 +800,8 @@ static void csr_free(kry_csr *A) {
                   A->data,   A->sdelta,   A->scbase,   A->cb_gptr,  A->cb_roff,   A->cb_col,
                   A->cb_val, A->dia_sptr, A->dia_width, A->dia_off, A->dia_mask, A->dia_val,
                   A->sp_sptr, A->sp_width, A->sp_cbase, A->sp_delta, A->sp_val,
-                  A->rs_sptr, A->rs_width, A->rs_colrank, A->rs_val, A->perm, A->iperm};
+                  A->rs_sptr, A->rs_width, A->rs_colrank, A->rs_val, A->perm, A->iperm,
+                  A->dia_uflag, A->dia_uval};
   for (void *b : bufs) dev_free(b);
 }
 
@@ -903,6 +914,10 @@ int kry_csr_compare(const kry_csr *A, const kry_csr *B, int64_t *out) {
     buf(A->indptr, B->indptr, A->nirregular ? (A->n + 1) * is : 0);
     buf(A->indices, B->indices, A->nirregular ? A->nnz * is : 0);
     buf(A->data, B->data, A->nirregular ? A->nnz * ds : 0);
+    // the uniform slot columns (bits 23, 24, 25): their count, the flags, the values
+    note(A->dia_nuniform != B->dia_nuniform);
+    buf(A->dia_uflag, B->dia_uflag, A->dia ? dc * 4 : 0);
+    buf(A->dia_uval, B->dia_uval, A->dia ? dc * ds : 0);
   }
   out[0] = nd;
   out[1] = mask;

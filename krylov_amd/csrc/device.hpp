@@ -563,11 +563,27 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(
 // The offsets of a slice ascend and every row is sorted, so each row is still
 // summed from 0 in stored order, one rounding per product and per add:
 // bitwise csr_matvec.
-template <typename V, typename MV, int UNR, class Src, class Epi>
+// A uniform slot column (kry_csr::dia_uflag: its present rows all store one
+// bit pattern, a constant-coefficient stencil's diagonals) takes that value
+// from its descriptor, a scalar load beside the offset and the masks, and its
+// 128 stored values are not read: the same (V)a * x per present row, so the
+// result is the same bits with the matrix stream gone. A round whose slot
+// columns are all uniform issues no value load at all (one scalar branch for
+// the round); a mixed round skips the uniform ones' loads one by one.
+// UNI (launch_spmv picks it from kry_csr::dia_nuniform): 1 = the operator has
+// uniform and streamed slot columns, as described; 0 = it has no uniform
+// column: no flag or value descriptor is read, the kernel of the images before
+// uniform columns existed; 2 = every slot column is uniform: no value load and
+// no flag, so far fewer registers than the general kernel and more resident
+// waves: with the matrix stream gone the kernel waits on each slice's chain
+// descriptors -> x loads -> store, not on HBM.
+template <typename V, typename MV, int UNR, class Src, class Epi, int UNI = 1>
 __global__ __launch_bounds__(kBlock) void spmv_dia_kernel(const int64_t *__restrict__ sptr,
                                                           const int *__restrict__ swidth,
                                                           const int *__restrict__ doff,
                                                           const uint64_t *__restrict__ dmask,
+                                                          const int *__restrict__ duflag,
+                                                          const MV *__restrict__ duval,
                                                           const MV *__restrict__ val, int64_t nslices, int64_t n,
                                                           Src src, Epi epi, double *__restrict__ part,
                                                           const Ctrl *ctrl, int step) {
@@ -604,28 +620,44 @@ __global__ __launch_bounds__(kBlock) void spmv_dia_kernel(const int64_t *__restr
     const int64_t c0 = base / kDiaSlice;
     const int *mo = doff + c0;  // wave-uniform: scalar loads
     const uint64_t *mk = dmask + 2 * c0;
+    const int *mu = duflag + c0;
+    const MV *mv = duval + c0;
     const MV *cv = val + base + 2 * lane;
     V acc0 = V(0), acc1 = V(0);
     for (int j0 = 0; j0 < w; j0 += UNR) {
       // descriptors: read unconditionally (the arrays are padded by kDiaPad
       // columns), all scalar loads in flight before the first use; values:
       // behind the wave-uniform `j0 + u < w` (a scalar branch, no wait)
-      int off[UNR];
+      int off[UNR], uf[UNR];
       uint64_t me[UNR], md[UNR];
+      MV uv[UNR];
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
         off[u] = mo[j0 + u];
         me[u] = mk[2 * (j0 + u)];
         md[u] = mk[2 * (j0 + u) + 1];
+        uf[u] = UNI == 1 ? mu[j0 + u] : UNI / 2;
+        uv[u] = UNI == 0 ? MV(0) : mv[j0 + u];
       }
-      MV a[UNR][2];
+      bool stream = false;  // a slot column of this round still has its values in memory
 #pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        if (j0 + u < w) {
-          pload_nt<MV>(cv + (int64_t)(j0 + u) * kDiaSlice, a[u]);
-        } else {
-          a[u][0] = MV(0);
-          a[u][1] = MV(0);
+      for (int u = 0; u < UNR; ++u) stream = stream || (j0 + u < w && uf[u] == 0);
+      MV a[UNR][2];
+      if (UNI == 2 || (UNI == 1 && !stream)) {
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+          a[u][0] = uv[u];  // past the slice's width: a later column's, dropped by on0 / on1 below
+          a[u][1] = uv[u];
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+          if (j0 + u < w && uf[u] == 0) {
+            pload_nt<MV>(cv + (int64_t)(j0 + u) * kDiaSlice, a[u]);
+          } else {
+            a[u][0] = uv[u];
+            a[u][1] = uv[u];
+          }
         }
       }
       bool on0[UNR], on1[UNR];
@@ -1660,20 +1692,39 @@ void launch_spmv(const kry_csr *A, int k, Src src, Epi epi, double *part, int *g
       // 2896 -> 3040 it/s). Narrow ones keep 8192 blocks: on cfg5 (7 slot
       // columns, fp32 values) the larger grid measured 1.8 % slower per
       // MINRES iteration, its consumers summing twice the partials.
+      // A wide image whose slot columns are all uniform streams no matrix
+      // values: its kernel (UNI = 2, 74 VGPRs, 6 waves per SIMD) waits on each
+      // slice's chain of descriptor, x and store latencies, and a wave that
+      // walks several slices overlaps one slice's epilogue with the next one's
+      // loads. Metric CG, ms per iteration by cap: 19683 (one slice per wave)
+      // 0.180, 8192 0.167, 6144 0.165, 5120 0.161, 4096 0.162, 3072 0.168,
+      // 2048 0.178 (profiles/dia_uniform_ab.md).
       static const int dia_cap_env = [] {
         const char *e = getenv("KRY_DIA_GRID");  // tuning override: grid cap
         return e ? std::max(1, std::min(atoi(e), kMaxGridBlk)) : 0;
       }();
-      const int dia_cap = dia_cap_env ? dia_cap_env : (A->dia_max_width > 8 ? kMaxGridBlk : kMaxGrid);
+      const bool allu = A->dia_nuniform > 0 && A->dia_nuniform == A->dia_nslots / kDiaSlice;
+      constexpr int kDiaGridUniform = 5120;
+      const int dia_cap = dia_cap_env                        ? dia_cap_env
+                          : A->dia_max_width <= 8            ? kMaxGrid
+                          : allu                             ? kDiaGridUniform
+                                                             : kMaxGridBlk;
       grid = (int)std::max<int64_t>(1, std::min<int64_t>(dia_cap, (A->dia_nslices + 3) / 4));
       auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, static_cast<const int64_t *>(A->dia_sptr),
                            static_cast<const int *>(A->dia_width), static_cast<const int *>(A->dia_off),
-                           static_cast<const uint64_t *>(A->dia_mask), static_cast<const MV *>(A->dia_val),
+                           static_cast<const uint64_t *>(A->dia_mask), static_cast<const int *>(A->dia_uflag),
+                           static_cast<const MV *>(A->dia_uval), static_cast<const MV *>(A->dia_val),
                            A->dia_nslices, A->n, src, epi, part, ctrl, step);
       };
-      if (A->dia_max_width <= 8) go(spmv_dia_kernel<V, MV, 8, Src, Epi>);
-      else go(spmv_dia_kernel<V, MV, 16, Src, Epi>);
+      // all uniform: 8 slot columns per round also for wide images (16 per
+      // round: 104 VGPRs, 4 waves per SIMD, metric CG 0.200 against 0.180 ms
+      // per iteration at one slice per wave)
+      if (allu) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 2>);
+      else if (A->dia_nuniform == 0 && A->dia_max_width <= 8) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 0>);
+      else if (A->dia_nuniform == 0) go(spmv_dia_kernel<V, MV, 16, Src, Epi, 0>);
+      else if (A->dia_max_width <= 8) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 1>);
+      else go(spmv_dia_kernel<V, MV, 16, Src, Epi, 1>);
       KRY_HIP(hipGetLastError());
       if (grid_out) *grid_out = grid;
       return;

@@ -19,7 +19,8 @@
 //                      offsets sorted (bitonic, in LDS) and made unique
 //   dia_fill_kernel    one block per slice: each entry's slot column by
 //                      binary search, its lane-mask bit (LDS atomicOr), its
-//                      value
+//                      value; then per slot column whether its present rows
+//                      all store one bit pattern (dia_build's uniform flag)
 // Slot pointers are exclusive scans of the per-slice slot counts
 // (hipcub::DeviceScan). Vector atomics only.
 #include <hipcub/hipcub.hpp>
@@ -206,13 +207,19 @@ __global__ __launch_bounds__(kDb) void dia_offsets_kernel(int64_t n, int64_t ns,
 }
 
 // DIA pass 2: one block per slice: slot column by binary search, lane mask
-// bits in LDS, values (holes stay 0 from the fill before)
+// bits in LDS, values (holes stay 0 from the fill before). Then (uniform != 0)
+// wave q takes slot columns q, q + 4, ...: lane l reads back the values of
+// rows 2l and 2l + 1 the block has just stored and compares their bits with
+// those of the column's lowest present row; a ballot decides, so the flag, the
+// value and the count do not depend on any order of execution.
 template <typename MV>
 __global__ __launch_bounds__(kDb) void dia_fill_kernel(int64_t n, const int32_t *__restrict__ ip,
                                                        const int32_t *__restrict__ ix, const MV *__restrict__ dv,
                                                        const long long *__restrict__ sptr, const int *__restrict__ width,
                                                        const int *__restrict__ offs, int32_t *doff, uint64_t *dmask,
-                                                       MV *dval) {
+                                                       MV *dval, int uniform, int32_t *uflag, MV *uval,
+                                                       unsigned long long *nuniform) {
+  using Bits = typename std::conditional<sizeof(MV) == 8, unsigned long long, unsigned>::type;
   __shared__ int o[kDiaWMax];
   __shared__ unsigned long long msk[2 * kDiaWMax];
   const int64_t s = blockIdx.x;
@@ -244,6 +251,29 @@ __global__ __launch_bounds__(kDb) void dia_fill_kernel(int64_t n, const int32_t 
     dmask[2 * (c0 + t)] = msk[2 * t];
     dmask[2 * (c0 + t) + 1] = msk[2 * t + 1];
   }
+  if (!uniform) return;
+  // the block's own stores to dval are visible to it after the barrier above
+  const int lane = t & 63;
+  unsigned nu = 0;
+  for (int j = t >> 6; j < w; j += kDb / 64) {
+    const unsigned long long me = msk[2 * j], md = msk[2 * j + 1];
+    if ((me | md) == 0ull) continue;
+    const int le = me ? __ffsll((long long)me) - 1 : 64, ld = md ? __ffsll((long long)md) - 1 : 64;
+    const int first = le <= ld ? 2 * le : 2 * ld + 1;  // the lowest present row
+    const MV *cv = dval + base + (int64_t)j * kDiaSlice;
+    const MV refv = cv[first];
+    const Bits ref = __builtin_bit_cast(Bits, refv);
+    const bool differ = (((me >> lane) & 1ull) && __builtin_bit_cast(Bits, cv[2 * lane]) != ref) ||
+                        (((md >> lane) & 1ull) && __builtin_bit_cast(Bits, cv[2 * lane + 1]) != ref);
+    if (__ballot(differ) == 0ull) {
+      if (lane == 0) {
+        uflag[c0 + j] = 1;
+        uval[c0 + j] = refv;
+      }
+      ++nu;
+    }
+  }
+  if (lane == 0 && nu) atomicAdd(nuniform, (unsigned long long)nu);
 }
 
 int grid_for_n(int64_t items, int per_block) {
@@ -385,14 +415,20 @@ int device_image_build(kry_csr *A, const int32_t *ip, const int32_t *ix, const M
       if (!(dslots * 4 > slots * 5 + (int64_t)4 * kDiaSlice * dmw)) {
         const int64_t dcols = dslots / kDiaSlice;
         Tmp doff((size_t)(dcols + kDiaPad) * 4), dmask((size_t)2 * (dcols + kDiaPad) * 8),
-            dval((size_t)(dslots + 2 * kDiaSlice) * sizeof(MV));
+            dval((size_t)(dslots + 2 * kDiaSlice) * sizeof(MV)), duflag((size_t)(dcols + kDiaPad) * 4),
+            duval((size_t)(dcols + kDiaPad) * sizeof(MV));
+        unsigned long long *dnuni = reinterpret_cast<unsigned long long *>(small.as<char>() + 112);
+        KRY_HIP(hipMemsetAsync(duflag.p, 0, (size_t)(dcols + kDiaPad) * 4, st));
+        KRY_HIP(hipMemsetAsync(duval.p, 0, (size_t)(dcols + kDiaPad) * sizeof(MV), st));
         KRY_HIP(hipMemsetAsync(doff.p, 0, (size_t)(dcols + kDiaPad) * 4, st));
         KRY_HIP(hipMemsetAsync(dmask.p, 0, (size_t)2 * (dcols + kDiaPad) * 8, st));
         KRY_HIP(hipMemsetAsync(dval.p, 0, (size_t)(dslots + 2 * kDiaSlice) * sizeof(MV), st));
         hipLaunchKernelGGL(dia_fill_kernel<MV>, dim3((unsigned)dns), dim3(kDb), 0, st, n, dip.as<int32_t>(),
                            dix.as<int32_t>(), ddv.as<MV>(), dsptr.as<const long long>(), dwidth.as<const int>(),
-                           offs.as<const int>(), doff.as<int32_t>(), dmask.as<uint64_t>(), dval.as<MV>());
+                           offs.as<const int>(), doff.as<int32_t>(), dmask.as<uint64_t>(), dval.as<MV>(),
+                           env_off("KRY_DIA_UNIFORM") ? 0 : 1, duflag.as<int32_t>(), duval.as<MV>(), dnuni);
         KRY_HIP(hipGetLastError());
+        A->dia_nuniform = (int64_t)read1(dnuni, st);
         A->dia = true;
         A->dia_nslices = dns;
         A->dia_nslots = dslots;
@@ -402,6 +438,8 @@ int device_image_build(kry_csr *A, const int32_t *ip, const int32_t *ix, const M
         A->dia_off = doff.release();
         A->dia_mask = dmask.release();
         A->dia_val = dval.release();
+        A->dia_uflag = duflag.release();
+        A->dia_uval = duval.release();
       }
     }
   }

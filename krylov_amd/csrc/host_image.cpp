@@ -11,6 +11,7 @@
 #include <cstring>
 #include <functional>
 #include <thread>
+#include <type_traits>
 
 namespace kry {
 
@@ -184,9 +185,23 @@ bool compact_fill(const std::vector<int64_t> &sptr, const std::vector<int32_t> &
 // col - row and sets the row's mask bit. Returns false (nothing built) for
 // unsorted or duplicate entries, or when the image would hold more than
 // 1.25x the SELL image's slots (offsets not shared across the slice's rows).
+// With `uniform`, pass 2 also flags every slot column whose present rows (the
+// mask bits; holes take no part) all store one bit pattern, and keeps that
+// value beside the flag (kry_csr::dia_uflag / dia_uval): bits are compared,
+// so -0.0 differs from +0.0 and NaNs compare by payload; a slot column with
+// one present row is uniform. A column that is not flagged keeps value 0.
+
+namespace {
+template <typename MV>
+inline uint64_t value_bits(MV v) {
+  typename std::conditional<sizeof(MV) == 8, uint64_t, uint32_t>::type b;
+  std::memcpy(&b, &v, sizeof(MV));
+  return b;
+}
+}  // namespace
 
 template <typename I, typename MV>
-bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_slots, DiaHost<MV> &d) {
+bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_slots, DiaHost<MV> &d, bool uniform) {
   if (sizeof(I) != 4 || n == 0) return false;
   constexpr int H = kDiaSlice;
   const int64_t ns = (n + H - 1) / H;
@@ -244,7 +259,11 @@ bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_s
   d.off.assign(cols + kDiaPad, 0);
   par_fill(d.mask, 2 * (cols + kDiaPad), (uint64_t)0);
   par_fill(d.val, slots + 2 * H, MV(0));
+  d.uflag.assign(cols + kDiaPad, 0);
+  d.uval.assign(cols + kDiaPad, MV(0));
+  std::atomic<int64_t> nuniform{0};
   auto pass2 = [&](int64_t sa, int64_t sb) {
+    int64_t nu = 0;
     for (int64_t s = sa; s < sb; ++s) {
       const std::vector<int32_t> &o = offs[s];
       const int64_t base = d.sptr[s], c0 = base / H;
@@ -261,13 +280,32 @@ bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_s
           ++j;
         }
       }
+      if (!uniform) continue;
+      for (size_t j = 0; j < o.size(); ++j) {
+        const uint64_t m[2] = {d.mask[2 * (c0 + j)], d.mask[2 * (c0 + j) + 1]};
+        const MV *v = d.val.data() + base + (int64_t)j * H;
+        int first = -1;  // the lowest present row
+        bool same = true;
+        for (int rl = 0; rl < H && same; ++rl) {
+          if (!((m[rl & 1] >> (rl >> 1)) & 1u)) continue;
+          if (first < 0) first = rl;
+          same = value_bits(v[rl]) == value_bits(v[first]);
+        }
+        if (first >= 0 && same) {
+          d.uflag[c0 + j] = 1;
+          d.uval[c0 + j] = v[first];
+          ++nu;
+        }
+      }
     }
+    nuniform += nu;
   };
   {
     std::vector<std::thread> th;
     for (unsigned t = 0; t < nt; ++t) th.emplace_back(pass2, ns * t / nt, ns * (t + 1) / nt);
     for (auto &x : th) x.join();
   }
+  d.nuniform = nuniform.load();
   return true;
 }
 
@@ -598,6 +636,26 @@ static void dia_plan_host(int64_t n, int64_t nnz, const I *ip, const I *ix, int6
   if (masks) std::copy(d.mask.begin(), d.mask.begin() + 2 * cols, masks);
 }
 
+// Host-only view of the uniform slot columns dia_build finds
+// (kry_dia_uniform_plan): info = {built, slot columns, uniform ones}, then the
+// flag and the value of every slot column.
+template <typename I, typename MV>
+static void dia_uniform_plan_host(int64_t n, int64_t nnz, const I *ip, const I *ix, const MV *dv, int64_t *info,
+                                  int32_t *flags, MV *values) {
+  check_csr(n, nnz, ip, ix);
+  int64_t ns = 0, sell_slots = 0, irr = 0;
+  sell_plan(n, ip, nullptr, nullptr, &ns, &sell_slots, &irr);
+  DiaHost<MV> d;
+  const bool built = dia_build(n, ip, ix, dv, sell_slots, d);
+  const int64_t cols = built ? d.sptr.back() / kDiaSlice : 0;
+  info[0] = built ? 1 : 0;
+  info[1] = cols;
+  info[2] = built ? d.nuniform : 0;
+  if (!built) return;
+  if (flags) std::copy(d.uflag.begin(), d.uflag.begin() + cols, flags);
+  if (values) std::memcpy(values, d.uval.data(), (size_t)cols * sizeof(MV));
+}
+
 // Column-blocked image (see kry_csr::cb_*). Returns false when not useful or
 // not possible: rows not sorted, x small enough to stay cache-resident, the
 // columns not scattered (most entries within half a block of the diagonal),
@@ -920,7 +978,7 @@ void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int3
 #define KRY_HOST_IM(I, MV)                                                                                         \
   template void sell_fill<I, MV>(int64_t, const I *, const I *, const MV *, const std::vector<int64_t> &,       \
                                  const std::vector<int32_t> &, hvec<I> &, hvec<MV> &);                          \
-  template bool dia_build<I, MV>(int64_t, const I *, const I *, const MV *, int64_t, DiaHost<MV> &);            \
+  template bool dia_build<I, MV>(int64_t, const I *, const I *, const MV *, int64_t, DiaHost<MV> &, bool);      \
   template bool cb_build<I, MV>(int64_t, const I *, const I *, const MV *, CbHost<MV> &);                       \
   template bool pair_build<I, MV>(int64_t, const I *, const I *, const MV *, int64_t, PairHost<MV> &);          \
   template void renumber_csr<I, MV>(int64_t, const I *, const I *, const MV *, const std::vector<int32_t> &,    \
@@ -1007,6 +1065,28 @@ int kry_dia_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices
                   offsets, masks);
   else
     throw Error{KRY_EINVAL, "bad itype"};
+  KRY_API_END
+}
+
+int kry_dia_uniform_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data, int dtype,
+                         int itype, int64_t *info, int32_t *flags, void *values) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(indptr && info && n >= 0 && nnz >= 0 && (nnz == 0 || (indices && data)), KRY_EINVAL,
+              "bad plan arguments");
+  KRY_REQUIRE(dtype == KRY_F32 || dtype == KRY_F64, KRY_EINVAL, "dtype must be f32 or f64");
+  KRY_REQUIRE(itype == KRY_I32 || itype == KRY_I64, KRY_EINVAL, "bad itype");
+  static const double zd = 0;
+  const void *dv = nnz ? data : (const void *)&zd;
+  auto go = [&](auto *ip, auto *ix) {
+    if (dtype == KRY_F64)
+      dia_uniform_plan_host(n, nnz, ip, ix, static_cast<const double *>(dv), info, flags, static_cast<double *>(values));
+    else
+      dia_uniform_plan_host(n, nnz, ip, ix, static_cast<const float *>(dv), info, flags, static_cast<float *>(values));
+  };
+  if (itype == KRY_I32)
+    go(static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices));
+  else
+    go(static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices));
   KRY_API_END
 }
 

@@ -74,10 +74,16 @@ struct DiaHost {
   hvec<uint64_t> mask;
   hvec<MV> val;
   int max_width = 0;
+  // per slot column (padded like off): 1 when its present rows all store one
+  // bit pattern, and that value (0 otherwise)
+  std::vector<int32_t> uflag;
+  std::vector<MV> uval;
+  int64_t nuniform = 0;
 };
 
 template <typename I, typename MV>
-bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_slots, DiaHost<MV> &d);
+bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_slots, DiaHost<MV> &d,
+               bool uniform = true);
 
 template <typename MV>
 struct CbHost {

@@ -80,6 +80,15 @@ struct kry_csr {
   void *dia_off = nullptr;    // int32, dia_nslots / kDiaSlice (+ kDiaPad)
   void *dia_mask = nullptr;   // uint64 x 2 per slot column: bit l of word q = row 2l + q present
   void *dia_val = nullptr;    // dtype, dia_nslots (+ pad), row order within a slot column; holes are 0
+  // uniform slot columns (constant-coefficient stencils): where every present
+  // row of a slot column stores one bit pattern, the k = 1 kernel takes the
+  // value from these descriptors (scalar loads, like dia_off) and never reads
+  // the column's lines of dia_val, which keep their full layout for the block
+  // kernel and the persistent loop. KRY_DIA_UNIFORM=0 at kry_csr_create: no
+  // column is flagged.
+  int64_t dia_nuniform = 0;   // flagged slot columns
+  void *dia_uflag = nullptr;  // int32, dia_nslots / kDiaSlice (+ kDiaPad): 1 = uniform
+  void *dia_uval = nullptr;   // dtype, dia_nslots / kDiaSlice (+ kDiaPad): the value, 0 when not flagged
   // paired-row SELL-128 image (general matrices, k = 1; spmv_pair_kernel):
   // slice s covers rows [128 s, 128 s + 128); slot column j of the slice
   // holds the j-th stored entry of every row, row r at position r - 128 s,

@@ -28,7 +28,8 @@ CFG5 = (8_000_000, 55_760_000)
 
 # leg of the index -> (summary file, (n, nnz), {key: (kernel-name prefix, note)})
 LEGS = {
-    "metric_cg": ("metric", METRIC, {"spmv": ("void kry::spmv_dia_kernel<double, double, 16, kry::SrcPlain", None),
+    # (the all-uniform instantiation since the uniform slot columns: <double, double, 8, ..., true>)
+    "metric_cg": ("metric", METRIC, {"spmv": ("void kry::spmv_dia_kernel<double, double, 8, kry::SrcPlain", None),
                                      "update": ("cg_upd_kernel", None)}),
     "spmv_general": ("general", METRIC, {"spmv": ("void kry::spmv_pair_kernel", None)}),
     "spmv_unstructured": ("unstructured", METRIC, {"spmv": ("void kry::spmv_rs1_kernel", None)}),
