@@ -269,7 +269,10 @@ int kry_vec_lincomb(kry_ctx *ctx, int form, kry_vec *z, kry_vec *x, kry_vec *y, 
  *         4 d = g(a); 5 d = value   (g(x) = x != 0 ? x : 1, np.where guard)
  * dot:   register d = inner(x, y) per column (w: weights or NULL).
  * lincomb: kry_vec_lincomb's forms with a = sa * reg[ra], b = sb * reg[rb]
- *         (register -1 = unused; sa, sb = +1 / -1).
+ *         (register -1 = unused; sa, sb = +1 / -1). As there, a form's own
+ *         operands are required: KRY_EINVAL for a null y (forms 0, 1, 2, 4,
+ *         5) or w (1, 2), and for ra = -1 (0, 1, 2, 3, 7) or rb = -1 (1, 2);
+ *         operands a form does not read are ignored and may be NULL / -1.
  * spmv:  y = A x.
  * check: register r against the criterion: mode 0 appends it to the chunk
  *         history and stops the chunk after this step when every column

@@ -27,6 +27,17 @@ enum {
   LC_COUNT = 8
 };
 
+// the operands a form reads (b goes with w); both entry points refuse a
+// form whose operand is missing
+struct LincombNeeds {
+  bool y, w, a;
+};
+inline LincombNeeds lincomb_needs(int form) {
+  const bool nest = form == LC_NEST_ADD || form == LC_NEST_SUB;
+  return {form == LC_AXPY || nest || form == LC_SUB || form == LC_ADD, nest,
+          form == LC_AXPY || nest || form == LC_DIV || form == LC_SCALE};
+}
+
 template <typename V>
 struct OpLincomb {
   V *z;
@@ -262,9 +273,8 @@ int kry_vec_lincomb(kry_ctx *ctx, int form, kry_vec *z, kry_vec *x, kry_vec *y, 
   KRY_API_BEGIN
   KRY_REQUIRE(ctx && z && x, KRY_EINVAL, "null argument");
   KRY_REQUIRE(form >= 0 && form < LC_COUNT, KRY_EINVAL, "unknown lincomb form");
-  const bool needs_y = form == LC_AXPY || form == LC_NEST_ADD || form == LC_NEST_SUB || form == LC_SUB || form == LC_ADD;
-  const bool needs_w = form == LC_NEST_ADD || form == LC_NEST_SUB;
-  const bool needs_a = form == LC_AXPY || form == LC_NEST_ADD || form == LC_NEST_SUB || form == LC_DIV || form == LC_SCALE;
+  const LincombNeeds nd = lincomb_needs(form);
+  const bool needs_y = nd.y, needs_w = nd.w, needs_a = nd.a;
   KRY_REQUIRE(!needs_y || y, KRY_EINVAL, "this form needs y");
   KRY_REQUIRE(!needs_w || w, KRY_EINVAL, "this form needs w");
   KRY_REQUIRE(!needs_a || a, KRY_EINVAL, "this form needs a");
@@ -410,31 +420,37 @@ int kry_prog_dot(kry_prog *p, kry_vec *x, kry_vec *y, kry_vec *w, int32_t d, int
   KRY_API_END
 }
 
-// z = form(x, y, w; sa * reg_a, sb * reg_b) (register -1: unused)
+// z = form(x, y, w; sa * reg_a, sb * reg_b) (register -1: unused; a form's
+// own y, w, ra, rb must be given, as in kry_vec_lincomb; the others are ignored)
 int kry_prog_lincomb(kry_prog *p, int32_t form, kry_vec *z, kry_vec *x, kry_vec *y, kry_vec *w, int32_t ra, double sa,
                      int32_t rb, double sb, int32_t step) {
   KRY_API_BEGIN
   KRY_REQUIRE(p && z && x && form >= 0 && form < LC_COUNT, KRY_EINVAL, "bad argument");
   KRY_REQUIRE(ra >= -1 && ra < p->nregs && rb >= -1 && rb < p->nregs, KRY_EINVAL, "bad register");
+  const LincombNeeds nd = lincomb_needs(form);
+  KRY_REQUIRE(!nd.y || y, KRY_EINVAL, "this form needs y");
+  KRY_REQUIRE(!nd.w || w, KRY_EINVAL, "this form needs w");
+  KRY_REQUIRE(!nd.a || ra >= 0, KRY_EINVAL, "this form needs the coefficient register ra");
+  KRY_REQUIRE(!nd.w || rb >= 0, KRY_EINVAL, "this form needs the coefficient register rb");
   check_same(z, x, "z / x");
-  if (y) check_same(y, x, "y / x");
-  if (w) check_same(w, x, "w / x");
+  if (nd.y) check_same(y, x, "y / x");
+  if (nd.w) check_same(w, x, "w / x");
   KRY_REQUIRE(x->k == p->k, KRY_EINVAL, "column count differs from the chain's");
   const int k = p->k;
   const int64_t N = x->n * (int64_t)k;
-  const double *a = ra >= 0 ? p->regs + (int64_t)ra * k : nullptr;
-  const double *b = rb >= 0 ? p->regs + (int64_t)rb * k : nullptr;
+  const double *a = nd.a ? p->regs + (int64_t)ra * k : nullptr;
+  const double *b = nd.w ? p->regs + (int64_t)rb * k : nullptr;
   if (x->dtype == KRY_F64)
     launch_elementwise<double>(N, k,
                                OpLincombD<double>{static_cast<double *>(z->d), static_cast<const double *>(x->d),
-                                                  y ? static_cast<const double *>(y->d) : nullptr,
-                                                  w ? static_cast<const double *>(w->d) : nullptr, a, b, sa, sb, form, k},
+                                                  nd.y ? static_cast<const double *>(y->d) : nullptr,
+                                                  nd.w ? static_cast<const double *>(w->d) : nullptr, a, b, sa, sb, form, k},
                                nullptr, p->ctrl, step, p->ctx->stream);
   else
     launch_elementwise<float>(N, k,
                               OpLincombD<float>{static_cast<float *>(z->d), static_cast<const float *>(x->d),
-                                                y ? static_cast<const float *>(y->d) : nullptr,
-                                                w ? static_cast<const float *>(w->d) : nullptr, a, b, sa, sb, form, k},
+                                                nd.y ? static_cast<const float *>(y->d) : nullptr,
+                                                nd.w ? static_cast<const float *>(w->d) : nullptr, a, b, sa, sb, form, k},
                               nullptr, p->ctrl, step, p->ctx->stream);
   KRY_API_END
 }
