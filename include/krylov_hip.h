@@ -39,6 +39,7 @@ typedef struct kry_minres kry_minres;
 typedef struct kry_comm kry_comm;
 typedef struct kry_prog kry_prog;
 typedef struct kry_tri kry_tri;
+typedef struct kry_precond kry_precond;
 
 /* value / index types */
 enum { KRY_F32 = 1, KRY_F64 = 2 };
@@ -342,6 +343,57 @@ int kry_tri_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, con
 int kry_tri_destroy(kry_tri *T);
 int kry_tri_info(const kry_tri *T, int64_t *info);
 int kry_tri_solve(kry_ctx *ctx, const kry_tri *T, const kry_vec *y, kry_vec *x);
+
+/* ---- factorised preconditioners: ILU(0) and the stage object (kry_version() >= 108)
+ * The reference takes any object with `@` as M / Ml / Mr (_helpers.py:83-90);
+ * its users hand it SSOR and incomplete-LU operators built on scipy
+ * spsolve_triangular. On the device those are a kry_precond: a short fixed
+ * sequence of stages on n x k vectors in the caller's numbering, each a
+ * kry_tri solve or a row scale by an (n,) vector (z = z * d). SSOR is lower
+ * solve, scale by D (2 - omega) / omega, upper solve; ILU(0) is L solve, U solve.
+ * kry_ilu0_plan (host-only, no device): the analysis of the factorisation of a
+ * CSR A with strictly sorted rows that all store their diagonal. Row i is
+ * eliminated with the rows k < i of its own pattern, so its levels and launch
+ * grouping are those of kry_tri_plan(lower = 1) on the pattern of tril(A).
+ * info[0..2] = levels, launches, rows of the largest level; when non-null:
+ * level[n] (from 1), order[n], launch[launches + 1] as kry_tri_plan's, and
+ * diag[n], the position of (i, i) in the CSR arrays. A row without a stored
+ * diagonal is KRY_ESINGULAR, an unsorted row KRY_EINVAL.
+ * kry_ilu0_factor: the factorisation on the device (int32 indices), in place
+ * over a copy of `data` returned in `values` (nnz values of `dtype`; the strict
+ * lower part is L, unit diagonal implied, the rest U). For rows i ascending:
+ *   for k in cols(i), k < i, ascending:
+ *     a_ik = a_ik / a_kk
+ *     for j in cols(i), j > k, with (k, j) stored: a_ij = a_ij - (a_ik * a_kj)
+ * with a true division and the product rounded before the subtraction (no
+ * FMA): bitwise that sequential loop, whatever the launch plan. One wavefront
+ * per row, one launch per run of levels as kry_tri_solve's (no kernel waits on
+ * another workgroup). info[0..2] as the plan's, info[3] = the smallest row whose
+ * pivot came out 0 or non-finite (-1: none); such a pivot is KRY_ESINGULAR.
+ * kry_precond_create / add_tri / add_scale / destroy: the stage list. Stages
+ * are borrowed: the caller keeps the kry_tri / kry_vec handles alive as long
+ * as the preconditioner, which must match them in n and dtype.
+ * kry_precond_apply: y = P x (k <= 64 columns, a power of two; y may alias x).
+ * kry_prog_precond: the same as a chain step.
+ * kry_*_set_precond: a factorised preconditioner in slot 0 = M, 1 = Ml, 2 = Mr
+ * (CG: 0 or 1) of a solver, after kry_*_set_preconditioners (which clears every
+ * slot) and before start. The preconditioner's dtype must be the vectors'; an
+ * operator renumbered at upload and a sharded solve are KRY_EUNSUPPORTED. The
+ * inner products a matrix preconditioner's SpMV fuses (cg.py:205-209,
+ * arnoldi.py:184-185) are taken by one element-wise pass after the stages. */
+int kry_ilu0_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int64_t *info,
+                  int32_t *level, int32_t *order, int32_t *launch, int64_t *diag);
+int kry_ilu0_factor(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,
+                    int dtype, int itype, void *values, int64_t *info);
+int kry_precond_create(kry_ctx *ctx, int64_t n, int dtype, kry_precond **out);
+int kry_precond_destroy(kry_precond *P);
+int kry_precond_add_tri(kry_precond *P, const kry_tri *T);
+int kry_precond_add_scale(kry_precond *P, const kry_vec *d);
+int kry_precond_apply(kry_ctx *ctx, const kry_precond *P, const kry_vec *x, kry_vec *y);
+int kry_prog_precond(kry_prog *p, const kry_precond *P, const kry_vec *x, kry_vec *y, int32_t step);
+int kry_cg_set_precond(kry_cg *s, int32_t slot, const kry_precond *P);
+int kry_gmres_set_precond(kry_gmres *s, int32_t slot, const kry_precond *P);
+int kry_minres_set_precond(kry_minres *s, int32_t slot, const kry_precond *P);
 
 /* Batched LAPACK >= 3.10 ?lartg on device (givens.py:35-40); host arrays of
  * `count` values of `dtype`. Bitwise equal to scipy.linalg.lapack ?lartg. */

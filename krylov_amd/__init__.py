@@ -23,6 +23,7 @@ from .sparse import CsrOperator, as_device_operator, clear_operator_cache
 from .stationary import gauss_seidel, jacobi, richardson, sor, ssor
 from .chebyshev import chebyshev
 from .triangular import TriangularOperator
+from .precond import Ilu0Preconditioner, SsorPreconditioner
 
 __version__ = "0.1.0"
 
@@ -45,6 +46,8 @@ __all__ = [
     "ssor",
     "chebyshev",
     "TriangularOperator",
+    "SsorPreconditioner",
+    "Ilu0Preconditioner",
     "givens",
     "Householder",
     "lartg",

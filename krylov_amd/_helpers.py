@@ -83,6 +83,11 @@ def _is_identity(M):
     return M is None or isinstance(M, Identity)
 
 
+def _is_factored(M):
+    """A factorised preconditioner object (krylov_amd.precond)."""
+    return getattr(M, "factored", False)
+
+
 class Problem:
     """Shapes and dtypes of one solve, mapped onto an n x kpad device block.
 
@@ -98,7 +103,8 @@ class Problem:
             if not _is_identity(op) and len(getattr(op, "shape", ())) != 2:
                 raise NotImplementedError(
                     f"preconditioner {name} must be None, Identity, a krylov_amd.CsrOperator, a scipy.sparse "
-                    f"matrix or a dense array on the MI355X path (got {type(op).__name__})"
+                    f"matrix, a dense array or a krylov_amd.SsorPreconditioner / Ilu0Preconditioner on the MI355X "
+                    f"path (got {type(op).__name__})"
                 )
         if np.iscomplexobj(b) or (x0 is not None and np.iscomplexobj(x0)):
             raise TypeError("complex right-hand sides are outside the MI355X path")
@@ -121,7 +127,21 @@ class Problem:
             if _is_identity(op):
                 self.ops[name] = None
                 continue
-            dop = as_device_operator(op, device=self.ctx.device, like=self.A, ctx=self.ctx)
+            if _is_factored(op):  # passed through: it applies itself (kry_precond)
+                dop = op
+                if dop.ctx is not self.ctx:
+                    raise ValueError(
+                        f"preconditioner {name} lives on device {dop.device}, the operator on {self.ctx.device}: "
+                        f"build it with device={self.ctx.device}"
+                    )
+                if self.A.renumbered:
+                    raise NotImplementedError(
+                        f"preconditioner {name} works in the caller's numbering, but the device renumbered the "
+                        "operator at upload (a scattered matrix with x over 8 MB); KRY_RENUMBER=0 keeps the caller's "
+                        "numbering"
+                    )
+            else:
+                dop = as_device_operator(op, device=self.ctx.device, like=self.A, ctx=self.ctx)
             if dop.shape != self.A.shape:
                 raise ValueError(f"preconditioner {name} has shape {dop.shape}, the operator {self.A.shape}")
             self.ops[name] = dop
@@ -142,6 +162,19 @@ class Problem:
         self.r0_dtype = np.dtype(r0)
         vt = np.result_type(r0, np.float64) if self.weights is not None else r0
         self.dtype = np.dtype(vt)
+        for name, op in self.ops.items():
+            if not _is_factored(op):
+                continue
+            if self.kpad > 64:
+                raise NotImplementedError(
+                    f"preconditioner {name}: a factorised preconditioner handles at most 64 right-hand-side columns; "
+                    "split the block"
+                )
+            if op.dtype != self.dtype:
+                raise ValueError(
+                    f"preconditioner {name} was built in {op.dtype}, this solve's device vectors are {self.dtype}: "
+                    f"build it with dtype=np.{self.dtype}"
+                )
         # dtype in which the reference's inner products (and norms) come out
         self.inner_dtype = np.dtype(np.float64) if self.weights is not None else self.dtype
         self.x0 = x0a
@@ -179,7 +212,12 @@ class Problem:
 
     def op_handles(self, *names):
         """ctypes handles of the named preconditioners (None = identity)."""
-        return [None if self.ops[nm] is None else self.ops[nm].handle for nm in names]
+        return [None if self.ops[nm] is None or _is_factored(self.ops[nm]) else self.ops[nm].handle for nm in names]
+
+    def factored_slots(self, *names):
+        """(slot, handle) of the named preconditioners that are factorised
+        objects, slot = the name's position (kry_*_set_precond)."""
+        return [(i, self.ops[nm].handle) for i, nm in enumerate(names) if _is_factored(self.ops[nm])]
 
     def has_precond(self):
         return any(op is not None for op in self.ops.values())

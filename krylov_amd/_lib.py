@@ -158,6 +158,17 @@ _SIGNATURES = {
     "kry_tri_destroy": [_vp],
     "kry_tri_info": [_vp, _ip64],
     "kry_tri_solve": [_vp, _vp, _vp, _vp],
+    "kry_ilu0_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp, _vp, _vp, _vp],
+    "kry_ilu0_factor": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _ip64],
+    "kry_precond_create": [_vp, _i64, _int, _pvp],
+    "kry_precond_destroy": [_vp],
+    "kry_precond_add_tri": [_vp, _vp],
+    "kry_precond_add_scale": [_vp, _vp],
+    "kry_precond_apply": [_vp, _vp, _vp, _vp],
+    "kry_prog_precond": [_vp, _vp, _vp, _vp, _i32],
+    "kry_cg_set_precond": [_vp, _i32, _vp],
+    "kry_gmres_set_precond": [_vp, _i32, _vp],
+    "kry_minres_set_precond": [_vp, _i32, _vp],
     "kry_mem_stats": [_ip64],
     "kry_mem_release": [],
 }
@@ -381,6 +392,27 @@ def tri_plan(indptr, indices, lower=True):
     check(lib.kry_tri_plan(*args, ptr(level), ptr(order), ptr(launch), ptr(widths)))
     return {"levels": int(info[0]), "launches": int(info[1]), "slices": int(info[2]), "slots": int(info[3]),
             "max_level": int(info[4]), "level": level, "order": order, "launch": launch, "widths": widths}
+
+
+def ilu0_plan(indptr, indices):
+    """Host-only analysis of the ILU(0) factorisation (kry_ilu0_plan):
+    {"levels", "launches", "max_level", "level" (per row, from 1), "order"
+    (rows by (level, row)), "launch" (level boundaries of the launches),
+    "diag" (each row's diagonal position in the CSR arrays)}."""
+    indptr = np.ascontiguousarray(indptr)
+    indices = np.ascontiguousarray(indices, dtype=indptr.dtype)
+    n, nnz = indptr.shape[0] - 1, indices.shape[0]
+    info = np.zeros(3, dtype=np.int64)
+    ip64 = info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    args = (n, nnz, ptr(indptr), ptr(indices), itype_code(indptr.dtype), ip64)
+    check(lib.kry_ilu0_plan(*args, None, None, None, None))
+    level = np.zeros(n, dtype=np.int32)
+    order = np.zeros(n, dtype=np.int32)
+    launch = np.zeros(int(info[1]) + 1, dtype=np.int32)
+    diag = np.zeros(n, dtype=np.int64)
+    check(lib.kry_ilu0_plan(*args, ptr(level), ptr(order), ptr(launch), ptr(diag)))
+    return {"levels": int(info[0]), "launches": int(info[1]), "max_level": int(info[2]), "level": level,
+            "order": order, "launch": launch, "diag": diag}
 
 
 def csr_layout(indptr):

@@ -37,6 +37,8 @@ class _CGState:
             raise TypeError("cg has no right preconditioner Mr")
         if prob.has_precond():
             check(lib.kry_cg_set_preconditioners(h, *prob.op_handles("M", "Ml")))
+            for slot, ph in prob.factored_slots("M", "Ml"):
+                check(lib.kry_cg_set_precond(h, slot, ph))
 
     def start(self):
         p = self.prob

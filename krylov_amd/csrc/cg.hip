@@ -24,6 +24,7 @@
 #include <tuple>
 #include <utility>
 
+#include "precond.hpp"
 #include "solver_common.hpp"
 
 using namespace kry;
@@ -37,7 +38,7 @@ struct kry_cg {
   bool scalar_f32 = false;
   void *b = nullptr, *x0 = nullptr, *y = nullptr, *r = nullptr, *p = nullptr;
   void *Ap = nullptr, *xk = nullptr, *rt = nullptr;
-  kry_csr *M = nullptr, *Ml = nullptr;  // preconditioners (null = identity)
+  PrecSlot M, Ml;  // preconditioners: a matrix or a kry_precond (empty = identity)
   void *z = nullptr;                    // M Ml_r (with M)
   void *t = nullptr;                    // A p / scratch (with Ml)
   double *w = nullptr;
@@ -1098,13 +1099,13 @@ int cg_residual_chain(kry_cg *s, const V *src, V *raw, V *mlr) {
   if (s->Ml) {
     launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiResidual<V>{bb, raw, s->w, k}, s->part, &P, nullptr, 0,
                           st);
-    launch_spmv_any<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
+    apply_prec<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
   } else {
     launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiResidual<V>{bb, mlr, s->w, k}, s->part, &P, nullptr, 0,
                           st);
   }
   if (s->M)
-    launch_spmv_any<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->z), mlr, s->w, k}, s->part,
+    apply_prec<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->z), mlr, s->w, k}, s->part,
                        &P, nullptr, 0, st);
   return P;
 }
@@ -1515,7 +1516,7 @@ bool cg_run_impl(kry_cg *s, int max_steps) {
       if (s->Ml) {  // Ap = Ml (A p) (Product(Ml, A), cg.py:110,180)
         V *t = static_cast<V *>(s->t);
         launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{p, k}, EpiStore<V>{t, k}, nullptr, nullptr, s->ctrl, step, st);
-        launch_spmv_any<V>(s->Ml, k, SrcPlain<V>{t, k}, EpiStoreDot<V>{static_cast<V *>(s->Ap), p, s->w, k}, partA,
+        apply_prec<V>(s->Ml, k, SrcPlain<V>{t, k}, EpiStoreDot<V>{static_cast<V *>(s->Ap), p, s->w, k}, partA,
                            &PA, s->ctrl, step, st);
       } else {
         launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{p, k}, EpiApDot<V>{static_cast<V *>(s->Ap), s->w, k}, partA, &PA,
@@ -1576,7 +1577,7 @@ bool cg_run_impl(kry_cg *s, int max_steps) {
       }
       if (s->M) {  // M_Ml_rk = M Ml_rk and <Ml_rk, M_Ml_rk> (cg.py:207-209)
         V *r = static_cast<V *>(s->r);
-        launch_spmv_any<V>(s->M, k, SrcPlain<V>{r, k}, EpiStoreDot<V>{static_cast<V *>(s->z), r, s->w, k}, partB,
+        apply_prec<V>(s->M, k, SrcPlain<V>{r, k}, EpiStoreDot<V>{static_cast<V *>(s->z), r, s->w, k}, partB,
                            &PB, s->ctrl, step, st);
       }
       if (s->scalar_f32)
@@ -1952,6 +1953,26 @@ int kry_cg_set_preconditioners(kry_cg *s, kry_csr *M, kry_csr *Ml) {
     KRY_HIP(hipMemsetAsync(s->t, 0, vb, s->ctx->stream));
   }
   KRY_HIP(hipStreamSynchronize(s->ctx->stream));
+  s->started = false;
+  KRY_API_END
+}
+
+// slot 0 = M, 1 = Ml: a factorised preconditioner in place of the slot's matrix
+int kry_cg_set_precond(kry_cg *s, int32_t slot, const kry_precond *P) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(s && P, KRY_EINVAL, "null argument");
+  KRY_REQUIRE(slot == 0 || slot == 1, KRY_EINVAL, "slot must be 0 (M) or 1 (Ml)");
+  precond_check(P, s->A, s->n, s->k, s->dtype);
+  KRY_REQUIRE(!s->comm, KRY_EUNSUPPORTED, "factorised preconditioners do not run on sharded solves");
+  KRY_HIP(hipSetDevice(s->ctx->device));
+  const size_t vb = ((size_t)s->n * s->k + 15) / 16 * 16 * dsize(s->dtype);
+  void *&buf = slot == 0 ? s->z : s->t;
+  if (!buf) {
+    buf = dev_alloc(vb);
+    KRY_HIP(hipMemsetAsync(buf, 0, vb, s->ctx->stream));
+    KRY_HIP(hipStreamSynchronize(s->ctx->stream));
+  }
+  (slot == 0 ? s->M : s->Ml) = P;
   s->started = false;
   KRY_API_END
 }

@@ -15,6 +15,7 @@
 //             (arnoldi.py:185-189, gmres.py:206-221)
 //   normalise V_{k+1} = w / guard(h[k+1])                       arnoldi.py:191-196
 // All scalars stay on the device; the host sees the residual-norm history.
+#include "precond.hpp"
 #include "solver_common.hpp"
 
 using namespace kry;
@@ -29,7 +30,7 @@ struct kry_gmres {
   int sweeps = 1;
   size_t vstride = 0;  // elements per basis vector (padded)
   void *b = nullptr, *x0 = nullptr, *V = nullptr, *wv = nullptr, *xk = nullptr, *rt = nullptr;
-  kry_csr *M = nullptr, *Ml = nullptr, *Mr = nullptr;  // preconditioners (null = identity)
+  PrecSlot M, Ml, Mr;  // preconditioners: a matrix or a kry_precond (empty = identity)
   void *P = nullptr;    // (maxiter + 1) basis vectors P_j (with M; else P = V)
   void *mw = nullptr;   // M w (with M)
   void *t1 = nullptr;   // Mr v / solution scratch (with Mr)
@@ -1446,13 +1447,13 @@ void gm_apply_op(kry_gmres *s, const V *v, Epi epi, double *part, int *P, const 
   const V *src = v;
   if (s->Mr) {
     V *t1 = static_cast<V *>(s->t1);
-    launch_spmv_any<V>(s->Mr, k, SrcPlain<V>{v, k}, EpiStore<V>{t1, k}, nullptr, nullptr, ctrl, step, st);
+    apply_prec<V>(s->Mr, k, SrcPlain<V>{v, k}, EpiStore<V>{t1, k}, nullptr, nullptr, ctrl, step, st);
     src = t1;
   }
   if (s->Ml) {
     V *t2 = static_cast<V *>(s->t2);
     launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiStore<V>{t2, k}, nullptr, nullptr, ctrl, step, st);
-    launch_spmv_any<V>(s->Ml, k, SrcPlain<V>{t2, k}, epi, part, P, ctrl, step, st);
+    apply_prec<V>(s->Ml, k, SrcPlain<V>{t2, k}, epi, part, P, ctrl, step, st);
   } else {
     launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, epi, part, P, ctrl, step, st);
   }
@@ -1469,9 +1470,9 @@ int gm_residual_chain(kry_gmres *s, const V *z, V *mlr) {
   launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{z, k}, EpiResidual<V>{static_cast<const V *>(s->b), raw, s->w, k},
                         s->part, &P, nullptr, 0, st);
   if (s->Ml)
-    launch_spmv_any<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
+    apply_prec<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
   if (s->M)
-    launch_spmv_any<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), mlr, s->w, k},
+    apply_prec<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), mlr, s->w, k},
                        s->part, &P, nullptr, 0, st);
   return P;
 }
@@ -1811,7 +1812,7 @@ void gm_run_impl(kry_gmres *s, int max_steps) {
     }
     P = Pin;
     if (s->M) {  // MAv = M Av, h[k+1] = sqrt(<Av, MAv>) (arnoldi.py:184-185)
-      launch_spmv_any<V>(s->M, k, SrcPlain<V>{w, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), w, s->w, k}, s->part,
+      apply_prec<V>(s->M, k, SrcPlain<V>{w, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), w, s->w, k}, s->part,
                          &P, s->ctrl, step, st);
       pin = s->part;
     }
@@ -1858,7 +1859,7 @@ void gm_solution_impl(kry_gmres *s) {
   V *t1 = static_cast<V *>(s->t1);
   launch_elementwise<V>(N, k, OpBasisCombo<V>{static_cast<const V *>(s->V), s->vstride, m, s->yy, nullptr, t1, k},
                         nullptr, nullptr, 0, st);
-  launch_spmv_any<V>(s->Mr, k, SrcPlain<V>{t1, k},
+  apply_prec<V>(s->Mr, k, SrcPlain<V>{t1, k},
                      EpiAddStore<V>{static_cast<V *>(s->xk), static_cast<const V *>(s->x0), k}, nullptr, nullptr,
                      nullptr, 0, st);
 }
@@ -1990,6 +1991,38 @@ int kry_gmres_set_preconditioners(kry_gmres *s, kry_csr *M, kry_csr *Ml, kry_csr
   }
   if (Mr) need(s->t1, vb);
   if (Ml) need(s->t2, vb);
+  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
+  s->started = false;
+  KRY_API_END
+}
+
+// slot 0 = M, 1 = Ml, 2 = Mr: a factorised preconditioner in place of the slot's matrix
+int kry_gmres_set_precond(kry_gmres *s, int32_t slot, const kry_precond *P) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(s && P, KRY_EINVAL, "null argument");
+  KRY_REQUIRE(slot >= 0 && slot <= 2, KRY_EINVAL, "slot must be 0 (M), 1 (Ml) or 2 (Mr)");
+  precond_check(P, s->A, s->n, s->k, s->dtype);
+  KRY_REQUIRE(!s->comm, KRY_EUNSUPPORTED, "factorised preconditioners do not run on sharded solves");
+  KRY_REQUIRE(!(slot == 0 && s->householder), KRY_EINVAL, "Householder Arnoldi does not take M (gmres.py:160)");
+  KRY_HIP(hipSetDevice(s->ctx->device));
+  const size_t vb = s->vstride * dsize(s->dtype);
+  auto need = [&](void *&buf, size_t bytes) {
+    if (!buf) {
+      buf = dev_alloc(bytes);
+      KRY_HIP(hipMemsetAsync(buf, 0, bytes, s->ctx->stream));
+    }
+  };
+  if (slot == 0) {
+    need(s->P, vb * ((size_t)s->maxiter + 1));
+    need(s->mw, vb);
+    s->M = P;
+  } else if (slot == 1) {
+    need(s->t2, vb);
+    s->Ml = P;
+  } else {
+    need(s->t1, vb);
+    s->Mr = P;
+  }
   KRY_HIP(hipStreamSynchronize(s->ctx->stream));
   s->started = false;
   KRY_API_END

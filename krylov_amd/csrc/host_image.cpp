@@ -965,12 +965,36 @@ void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int3
     }
 }
 
+// ------------------------------------------------------------ ILU(0) plan
+template <typename I>
+void ilu0_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, Ilu0Plan &p) {
+  check_csr(n, nnz, ip, ix);
+  p = Ilu0Plan();
+  p.diag.assign((size_t)n, -1);
+  // the pattern of tril(A): every row up to and including its diagonal
+  std::vector<I> lp((size_t)n + 1, 0), lx;
+  lx.reserve((size_t)nnz / 2 + (size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    for (int64_t e = (int64_t)ip[i]; e < (int64_t)ip[i + 1]; ++e) {
+      const int64_t j = (int64_t)ix[e];
+      KRY_REQUIRE(e == (int64_t)ip[i] || (int64_t)ix[e - 1] < j, KRY_EINVAL,
+                  "ILU(0) needs sorted rows without duplicates (row " + std::to_string(i) + ")");
+      if (j <= i) lx.push_back(ix[e]);
+      if (j == i) p.diag[(size_t)i] = e;
+    }
+    KRY_REQUIRE(p.diag[(size_t)i] >= 0, KRY_ESINGULAR, "singular matrix: no diagonal entry in row " + std::to_string(i));
+    lp[(size_t)i + 1] = (I)lx.size();
+  }
+  tri_plan(n, (int64_t)lx.size(), lp.data(), lx.data(), true, p.tri);
+}
+
 // explicit instantiations: the combinations kry_csr_create dispatches
 #define KRY_HOST_I(I)                                                                                             \
   template void check_csr<I>(int64_t, int64_t, const I *, const I *);                                            \
   template bool scattered<I>(int64_t, const I *, const I *);                                                     \
   template bool rcm_order<I>(int64_t, const I *, const I *, int64_t, std::vector<int32_t> &, int64_t *);          \
   template void tri_plan<I>(int64_t, int64_t, const I *, const I *, bool, TriPlan &);                            \
+  template void ilu0_plan<I>(int64_t, int64_t, const I *, const I *, Ilu0Plan &);                               \
   template void sell_plan<I>(int64_t, const I *, std::vector<int64_t> *, std::vector<int32_t> *, int64_t *,     \
                              int64_t *, int64_t *);                                                              \
   template bool compact_fill<I>(const std::vector<int64_t> &, const std::vector<int32_t> &, const hvec<I> &,     \
@@ -1176,6 +1200,27 @@ int kry_tri_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices
   if (order) std::copy(p.order.begin(), p.order.end(), order);
   if (launch) std::copy(p.launch.begin(), p.launch.end(), launch);
   if (widths) std::copy(p.swidth.begin(), p.swidth.end(), widths);
+  KRY_API_END
+}
+
+int kry_ilu0_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int64_t *info,
+                  int32_t *level, int32_t *order, int32_t *launch, int64_t *diag) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(indptr && info && n >= 0 && nnz >= 0 && (nnz == 0 || indices), KRY_EINVAL, "bad plan arguments");
+  Ilu0Plan p;
+  if (itype == KRY_I32)
+    ilu0_plan(n, nnz, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices), p);
+  else if (itype == KRY_I64)
+    ilu0_plan(n, nnz, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices), p);
+  else
+    throw Error{KRY_EINVAL, "bad itype"};
+  info[0] = p.tri.nlevels;
+  info[1] = (int64_t)p.tri.launch.size() - 1;
+  info[2] = p.tri.max_level_rows;
+  if (level) std::copy(p.tri.level.begin(), p.tri.level.end(), level);
+  if (order) std::copy(p.tri.order.begin(), p.tri.order.end(), order);
+  if (launch) std::copy(p.tri.launch.begin(), p.tri.launch.end(), launch);
+  if (diag) std::copy(p.diag.begin(), p.diag.end(), diag);
   KRY_API_END
 }
 

@@ -196,4 +196,18 @@ template <typename I, typename V>
 void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int32_t> &rows, hvec<V> &diag,
               hvec<int32_t> &col, hvec<V> &val);
 
+// ILU(0) factorisation in place over A's pattern (precond.hip): the analysis
+// of a square CSR A with strictly sorted rows that all store their diagonal.
+// Row i is eliminated with the rows k < i of its own pattern, so its level is
+// the one tri_plan(lower) gives the pattern of tril(A): `tri` is that plan
+// (levels, order, lrow and the launch grouping; its slices are not used by
+// the factorisation). diag[i] = the position of (i, i) in the CSR arrays.
+// A row without a stored diagonal is KRY_ESINGULAR, an unsorted row KRY_EINVAL.
+struct Ilu0Plan {
+  TriPlan tri;
+  std::vector<int64_t> diag;  // n
+};
+template <typename I>
+void ilu0_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, Ilu0Plan &p);
+
 }  // namespace kry

@@ -17,6 +17,7 @@
 // Precision follows the reference under NumPy-2 promotion: Lanczos scalars
 // in the vector dtype, the inner products in the inner's dtype, R / rotations
 // / y / z / W in float64 (minres.py:195, 219).
+#include "precond.hpp"
 #include "solver_common.hpp"
 
 using namespace kry;
@@ -31,7 +32,7 @@ struct kry_minres {
   void *b = nullptr, *x0 = nullptr, *yk = nullptr, *wv = nullptr, *xk = nullptr, *rt = nullptr;
   void *P[3] = {nullptr, nullptr, nullptr};  // ring: p_old, p (= v), p_new
   double *W[2] = {nullptr, nullptr};         // float64 W ring
-  kry_csr *M = nullptr, *Ml = nullptr, *Mr = nullptr;  // preconditioners (null = identity)
+  PrecSlot M, Ml, Mr;  // preconditioners: a matrix or a kry_precond (empty = identity)
   void *Vr[2] = {nullptr, nullptr};  // v = M p ring (with M; else v = p)
   void *mw = nullptr;                // M w (with M)
   void *t1 = nullptr, *t2 = nullptr; // Mr v (with Mr), A Mr v / raw residual (with Ml)
@@ -500,13 +501,13 @@ void mr_apply_op(kry_minres *s, const V *v, Epi epi, double *part, int *P, const
   const V *src = v;
   if (s->Mr) {
     V *t1 = static_cast<V *>(s->t1);
-    launch_spmv_any<V>(s->Mr, k, SrcPlain<V>{v, k}, EpiStore<V>{t1, k}, nullptr, nullptr, ctrl, step, st);
+    apply_prec<V>(s->Mr, k, SrcPlain<V>{v, k}, EpiStore<V>{t1, k}, nullptr, nullptr, ctrl, step, st);
     src = t1;
   }
   if (s->Ml) {
     V *t2 = static_cast<V *>(s->t2);
     launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiStore<V>{t2, k}, nullptr, nullptr, ctrl, step, st);
-    launch_spmv_any<V>(s->Ml, k, SrcPlain<V>{t2, k}, epi, part, P, ctrl, step, st);
+    apply_prec<V>(s->Ml, k, SrcPlain<V>{t2, k}, epi, part, P, ctrl, step, st);
   } else {
     launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, epi, part, P, ctrl, step, st);
   }
@@ -523,9 +524,9 @@ int mr_residual_chain(kry_minres *s, const V *z, V *mlr) {
   launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{z, k}, EpiResidual<V>{static_cast<const V *>(s->b), raw, s->w, k},
                         s->part, &P, nullptr, 0, st);
   if (s->Ml)
-    launch_spmv_any<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
+    apply_prec<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
   if (s->M)
-    launch_spmv_any<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), mlr, s->w, k},
+    apply_prec<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), mlr, s->w, k},
                        s->part, &P, nullptr, 0, st);
   return P;
 }
@@ -537,7 +538,7 @@ void mr_compute_xk(kry_minres *s) {
   const int k = s->k;
   const int64_t N = s->n * (int64_t)k;
   if (s->Mr)
-    launch_spmv_any<V>(s->Mr, k, SrcPlain<V>{static_cast<const V *>(s->yk), k},
+    apply_prec<V>(s->Mr, k, SrcPlain<V>{static_cast<const V *>(s->yk), k},
                        EpiAddStore<V>{static_cast<V *>(s->xk), static_cast<const V *>(s->x0), k}, nullptr, nullptr,
                        nullptr, 0, st);
   else
@@ -676,7 +677,7 @@ void mr_run_typed(kry_minres *s, int max_steps) {
     PB = launch_elementwise<V>(N, k, OpLanczosOrtho<V, S>{w, p, s->scal + M_ALPHA * k, s->w, k, s->M ? 1 : 0},
                                s->M ? nullptr : partB, s->ctrl, step, st);
     if (s->M)  // MAv = M Av, h[2] = sqrt(<Av, MAv>) (arnoldi.py:268-269)
-      launch_spmv_any<V>(s->M, k, SrcPlain<V>{w, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), w, s->w, k}, partB, &PB,
+      apply_prec<V>(s->M, k, SrcPlain<V>{w, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), w, s->w, k}, partB, &PB,
                          s->ctrl, step, st);
     hipLaunchKernelGGL((mr_qr_kernel<V, S>), dim3(1), dim3(kBlock), 0, st, partB, PB, k, s->scal, i >= 1 ? 1 : 0,
                        i >= 2 ? 1 : 0, s->hist, s->ctrl, step, s->comm ? s->gbuf : nullptr, s->col_offset,
@@ -819,6 +820,38 @@ int kry_minres_set_preconditioners(kry_minres *s, kry_csr *M, kry_csr *Ml, kry_c
   }
   if (Mr) need(s->t1);
   if (Ml) need(s->t2);
+  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
+  s->started = false;
+  KRY_API_END
+}
+
+// slot 0 = M, 1 = Ml, 2 = Mr: a factorised preconditioner in place of the slot's matrix
+int kry_minres_set_precond(kry_minres *s, int32_t slot, const kry_precond *P) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(s && P, KRY_EINVAL, "null argument");
+  KRY_REQUIRE(slot >= 0 && slot <= 2, KRY_EINVAL, "slot must be 0 (M), 1 (Ml) or 2 (Mr)");
+  precond_check(P, s->A, s->n, s->k, s->dtype);
+  KRY_REQUIRE(!s->comm, KRY_EUNSUPPORTED, "factorised preconditioners do not run on sharded solves");
+  KRY_HIP(hipSetDevice(s->ctx->device));
+  const size_t vb = ((size_t)s->n * s->k + 15) / 16 * 16 * dsize(s->dtype);
+  auto need = [&](void *&buf) {
+    if (!buf) {
+      buf = dev_alloc(vb);
+      KRY_HIP(hipMemsetAsync(buf, 0, vb, s->ctx->stream));
+    }
+  };
+  if (slot == 0) {
+    need(s->Vr[0]);
+    need(s->Vr[1]);
+    need(s->mw);
+    s->M = P;
+  } else if (slot == 1) {
+    need(s->t2);
+    s->Ml = P;
+  } else {
+    need(s->t1);
+    s->Mr = P;
+  }
   KRY_HIP(hipStreamSynchronize(s->ctx->stream));
   s->started = false;
   KRY_API_END

@@ -1,0 +1,173 @@
+// Factorised preconditioners (kry_precond, precond.hip) as the solver cores
+// see them: a preconditioner slot M / Ml / Mr holds either a matrix (kry_csr,
+// one SpMV with the fused epilogue) or a kry_precond (a short sequence of
+// triangular solves and row scales), and apply_prec serves both.
+#pragma once
+
+#include <vector>
+
+#include "solver_common.hpp"
+
+struct kry_tri;
+
+// A stage is a triangular solve (tri) or a row scale by an (n,) device vector
+// of the preconditioner's dtype (scale). The stages are borrowed: the caller
+// keeps the kry_tri / kry_vec handles alive while the preconditioner is.
+struct kry_precond {
+  struct Stage {
+    const kry_tri *tri = nullptr;
+    const void *scale = nullptr;
+  };
+  kry_ctx *ctx = nullptr;
+  int64_t n = 0;
+  int dtype = 0;
+  std::vector<Stage> stages;
+};
+
+namespace kry {
+
+// tri.hip: kry_tri_solve on raw n x k blocks (k a power of two <= 64; x may alias y)
+void tri_solve_raw(const kry_tri *T, int k, const void *y, void *x, const Ctrl *ctrl, int step, hipStream_t st);
+void tri_shape(const kry_tri *T, int64_t *n, int *dtype);
+// precond.hip: dst = P src, stage by stage (the first stage reads src, the
+// others work in place on dst; dst may alias src)
+void precond_stages(const kry_precond *P, int k, const void *src, void *dst, const Ctrl *ctrl, int step,
+                    hipStream_t st);
+// what every set_precond of the cores checks
+void precond_check(const kry_precond *P, const kry_csr *A, int64_t n, int k, int dtype);
+
+// A preconditioner slot of a solver. It converts to bool like the kry_csr
+// pointer it replaces, so `!s->M` and `s->M ? a : b` see both kinds.
+struct PrecSlot {
+  kry_csr *mat = nullptr;
+  const kry_precond *fac = nullptr;
+  explicit operator bool() const { return mat != nullptr || fac != nullptr; }
+  PrecSlot &operator=(kry_csr *m) {
+    mat = m;
+    fac = nullptr;
+    return *this;
+  }
+  PrecSlot &operator=(const kry_precond *p) {
+    mat = nullptr;
+    fac = p;
+    return *this;
+  }
+};
+
+// the inner-product partials a fused epilogue would have written: <q, y>_w
+template <typename V>
+struct OpPrecDot {
+  const V *q, *y;
+  const double *w;
+  int k;
+  __device__ __forceinline__ void operator()(int64_t e, int64_t N, double (&acc)[Vec16<V>::W]) const {
+    constexpr int W = Vec16<V>::W;
+    V a[W], b[W];
+    VIO<V>::load(q, e, N, a);
+    VIO<V>::load(y, e, N, b);
+#pragma unroll
+    for (int v = 0; v < W; ++v)
+      if (e + v < N)
+        acc[v] += w ? dterm_w((double)a[v], w[(e + v) / k], (double)b[v]) : dterm((double)a[v], (double)b[v]);
+  }
+};
+
+// out = x0 + out (EpiAddStore's sum)
+template <typename V>
+struct OpPrecAdd {
+  V *out;
+  const V *x0;
+  __device__ __forceinline__ void operator()(int64_t e, int64_t N, double (&)[Vec16<V>::W]) const {
+    constexpr int W = Vec16<V>::W;
+    V a[W], b[W];
+    VIO<V>::load(x0, e, N, a);
+    VIO<V>::load(out, e, N, b);
+#pragma unroll
+    for (int v = 0; v < W; ++v) b[v] = a[v] + b[v];
+    VIO<V>::store(out, e, N, b);
+  }
+};
+
+// out = out - h0 * pold and <v, out>_w (EpiLanczos on a finished product)
+template <typename V>
+struct OpPrecLanczos {
+  V *out;
+  const V *v, *pold;
+  const double *h0, *w;
+  int k;
+  __device__ __forceinline__ void operator()(int64_t e, int64_t N, double (&acc)[Vec16<V>::W]) const {
+    constexpr int W = Vec16<V>::W;
+    V o[W], vv[W], po[W];
+    VIO<V>::load(out, e, N, o);
+    VIO<V>::load(v, e, N, vv);
+    if (pold) {
+      VIO<V>::load(pold, e, N, po);
+#pragma unroll
+      for (int c = 0; c < W; ++c) {
+        const V t = (V)h0[(e + c) & (k - 1)] * po[c];
+        o[c] = o[c] - t;
+      }
+      VIO<V>::store(out, e, N, o);
+    }
+#pragma unroll
+    for (int c = 0; c < W; ++c)
+      if (e + c < N)
+        acc[c] += w ? dterm_w((double)vv[c], w[(e + c) / k], (double)o[c]) : dterm((double)vv[c], (double)o[c]);
+  }
+};
+
+// The factorised form of each epilogue the cores fuse into a preconditioner
+// product: the stages run into the epilogue's destination, then one
+// element-wise pass does what the epilogue adds (partials in the layout of
+// elementwise_kernel, which the rho / norm kernels already read).
+template <typename V>
+void prec_factored(const kry_precond *P, int k, const V *src, const EpiStore<V> &epi, double *, int *grid_out,
+                   const Ctrl *ctrl, int step, hipStream_t st) {
+  precond_stages(P, k, src, epi.y, ctrl, step, st);
+  if (grid_out) *grid_out = 0;
+}
+template <typename V>
+void prec_factored(const kry_precond *P, int k, const V *src, const EpiStoreNorm<V> &epi, double *part, int *grid_out,
+                   const Ctrl *ctrl, int step, hipStream_t st) {
+  precond_stages(P, k, src, epi.y, ctrl, step, st);
+  const int g = launch_elementwise<V>(P->n * (int64_t)k, k, OpPrecDot<V>{epi.y, epi.y, epi.w, k}, part, ctrl, step, st);
+  if (grid_out) *grid_out = g;
+}
+template <typename V>
+void prec_factored(const kry_precond *P, int k, const V *src, const EpiStoreDot<V> &epi, double *part, int *grid_out,
+                   const Ctrl *ctrl, int step, hipStream_t st) {
+  KRY_REQUIRE(epi.q != epi.y, KRY_EINVAL, "the factorised preconditioner's destination aliases the dot operand");
+  precond_stages(P, k, src, epi.y, ctrl, step, st);
+  const int g = launch_elementwise<V>(P->n * (int64_t)k, k, OpPrecDot<V>{epi.q, epi.y, epi.w, k}, part, ctrl, step, st);
+  if (grid_out) *grid_out = g;
+}
+template <typename V>
+void prec_factored(const kry_precond *P, int k, const V *src, const EpiAddStore<V> &epi, double *, int *grid_out,
+                   const Ctrl *ctrl, int step, hipStream_t st) {
+  KRY_REQUIRE(epi.x0 != epi.out, KRY_EINVAL, "the factorised preconditioner's destination aliases x0");
+  precond_stages(P, k, src, epi.out, ctrl, step, st);
+  if (epi.x0) launch_elementwise<V>(P->n * (int64_t)k, k, OpPrecAdd<V>{epi.out, epi.x0}, nullptr, ctrl, step, st);
+  if (grid_out) *grid_out = 0;
+}
+
+template <typename V>
+void prec_factored(const kry_precond *P, int k, const V *src, const EpiLanczos<V> &epi, double *part, int *grid_out,
+                   const Ctrl *ctrl, int step, hipStream_t st) {
+  KRY_REQUIRE(epi.v != epi.out && epi.pold != epi.out, KRY_EINVAL,
+              "the factorised preconditioner's destination aliases a Lanczos vector");
+  precond_stages(P, k, src, epi.out, ctrl, step, st);
+  const int g = launch_elementwise<V>(P->n * (int64_t)k, k,
+                                      OpPrecLanczos<V>{epi.out, epi.v, epi.pold, epi.h0, epi.w, k}, part, ctrl, step, st);
+  if (grid_out) *grid_out = g;
+}
+
+// Every preconditioner product of the cores: a matrix slot makes exactly the
+// SpMV call it always made, a factorised one runs its stages.
+template <typename V, class Epi>
+void apply_prec(const PrecSlot &S, int k, SrcPlain<V> src, Epi epi, double *part, int *grid_out, const Ctrl *ctrl,
+                int step, hipStream_t st) {
+  if (S.fac) return prec_factored<V>(S.fac, k, src.x, epi, part, grid_out, ctrl, step, st);
+  launch_spmv_any<V>(S.mat, k, src, epi, part, grid_out, ctrl, step, st);
+}
+
+}  // namespace kry

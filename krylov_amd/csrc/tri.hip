@@ -18,6 +18,7 @@
 // kernel waits on another workgroup: stream order is the only cross-workgroup
 // dependency.
 #include "host_image.hpp"
+#include "precond.hpp"
 #include "prog.hpp"
 
 using namespace kry;
@@ -180,6 +181,28 @@ void tri_build(kry_tri *T, int64_t n, int64_t nnz, const I *ip, const I *ix, con
 }
 
 }  // namespace
+
+namespace kry {
+
+// the solve on raw n x k blocks of a solver core or a kry_precond stage (precond.hpp)
+void tri_solve_raw(const kry_tri *T, int k, const void *y, void *x, const Ctrl *ctrl, int step, hipStream_t st) {
+  kry_vec yv, xv;
+  yv.n = xv.n = T->n;
+  yv.k = xv.k = k;
+  yv.dtype = xv.dtype = T->dtype;
+  yv.d = const_cast<void *>(y);
+  xv.d = x;
+  tri_check(T, &yv, &xv);
+  if (T->dtype == KRY_F64) tri_launch<double>(T, &yv, &xv, ctrl, step, st);
+  else tri_launch<float>(T, &yv, &xv, ctrl, step, st);
+}
+
+void tri_shape(const kry_tri *T, int64_t *n, int *dtype) {
+  *n = T->n;
+  *dtype = T->dtype;
+}
+
+}  // namespace kry
 
 #define KRY_API_BEGIN try {
 #define KRY_API_END                  \

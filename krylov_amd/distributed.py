@@ -26,6 +26,7 @@ from ._helpers import Info, Problem
 from ._lib import check, lib
 from .cg import _CGState
 from .device import get_context
+from .precond import refuse_sharded
 from .shard import ShardLayout, drive, file_rendezvous
 
 
@@ -187,6 +188,7 @@ def _hook(callback, first, step):
 
 
 def _problem(A, B, x0, inner, comm, M=None, Ml=None, Mr=None):
+    refuse_sharded(M=M, Ml=Ml, Mr=Mr)
     return Problem(A, _block(B), x0, inner, M=M, Ml=Ml, Mr=Mr, device=comm.ctx.device)
 
 

@@ -186,7 +186,12 @@ class _Chain:
     def apply(self, name, x, out, st):
         """op @ x into `out` (the reference's Identity: x itself)."""
         op = self.D.prob.ops[name]
-        return x if op is None else self.spmv(op, x, out, st)
+        if op is None:
+            return x
+        if _helpers._is_factored(op):  # a kry_precond: its stages as chain steps
+            check(lib.kry_prog_precond(self.h, op.handle, x.handle, out.handle, st))
+            return out
+        return self.spmv(op, x, out, st)
 
     def norm(self, v, tmp, d, st, M=None):
         """d = sqrt(<v, M v>) (M None: <v, v>)."""

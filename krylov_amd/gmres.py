@@ -60,6 +60,8 @@ class _GmresState:
         self._fin = _lib.own(self, lib.kry_gmres_destroy, h)
         if prob.has_precond():
             check(lib.kry_gmres_set_preconditioners(h, *prob.op_handles("M", "Ml", "Mr")))
+            for slot, ph in prob.factored_slots("M", "Ml", "Mr"):
+                check(lib.kry_gmres_set_precond(h, slot, ph))
 
     def start(self, x0_dev=None):
         """r0 = b - A x0 on the device; x0 = the problem's own x0 or, for a

@@ -23,6 +23,8 @@ class _MinresState:
         self._fin = _lib.own(self, lib.kry_minres_destroy, h)
         if prob.has_precond():
             check(lib.kry_minres_set_preconditioners(h, *prob.op_handles("M", "Ml", "Mr")))
+            for slot, ph in prob.factored_slots("M", "Ml", "Mr"):
+                check(lib.kry_minres_set_precond(h, slot, ph))
 
     def start(self):
         p = self.prob

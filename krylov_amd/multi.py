@@ -95,6 +95,7 @@ def solve(method, A, B, devices, x0=None, **kw):
     ``devices``: returns ``(xk or None, Info)`` with ``Info.xk`` the gathered
     global iterate and ``Info.resnorms`` the global history."""
     callback = kw.pop("callback", None)
+    distributed.refuse_sharded(**{name: kw.get(name) for name in ("M", "Ml", "Mr")})
     devices = [int(d) for d in devices]
     if len(set(devices)) != len(devices) or not devices:
         raise ValueError(f"devices must be distinct device ids, got {devices}")

@@ -1,0 +1,213 @@
+"""Factorised preconditioners on the device: ``SsorPreconditioner`` and
+``Ilu0Preconditioner``, objects that go where a matrix goes as ``M`` / ``Ml``
+/ ``Mr`` of cg, gmres, gmres_restarted, minres, bicgstab, cgs, cgr and
+chebyshev (the reference takes any object with ``@`` there, _helpers.py:83-90,
+and its users hand it SSOR and incomplete-LU operators built on scipy
+``spsolve_triangular``).
+
+Both are a ``kry_precond`` (csrc/precond.hip): a short fixed sequence of
+``TriangularOperator`` solves and row scales on the solve's n x k device
+vectors, in the caller's numbering.
+
+* SSOR: ``M r = (D/w + U)^-1 [D (2 - w)/w] (D/w + L)^-1 r``: lower solve, row
+  scale, upper solve (the factor (2 - w)/w is folded into the scale vector).
+* ILU(0): ``M r = U^-1 L^-1 r`` with L, U factorised on the device
+  (``kry_ilu0_factor``), bitwise the sequential loop over A's pattern.
+
+A solve with one of them runs in the caller's numbering, so an operator the
+device renumbered at upload is refused (``KRY_RENUMBER=0`` keeps the caller's
+numbering), as are more than 64 right-hand-side columns and the multi-GPU
+drivers.
+"""
+import ctypes
+import time
+
+import numpy as np
+import scipy.sparse
+
+from . import _lib
+from ._lib import check, lib
+from .device import DeviceVector, get_context
+from .sparse import CsrOperator, _next_pow2
+from .triangular import MAX_COLS, TriangularOperator
+
+
+def _canonical(A, name, dtype):
+    """A as a canonical square real CSR of the preconditioner's dtype."""
+    if isinstance(A, CsrOperator):
+        raise TypeError(
+            f"{name} needs the matrix's diagonal / triangle, which a CsrOperator does not keep: pass the scipy.sparse "
+            "matrix or dense array itself (its device copy is cached, so this costs no second upload)"
+        )
+    if not (scipy.sparse.issparse(A) or (isinstance(A, np.ndarray) and A.ndim == 2)):
+        raise TypeError(f"{name} needs a scipy.sparse matrix or a dense 2-D array, not {type(A).__name__}")
+    if np.iscomplexobj(A.data if scipy.sparse.issparse(A) else A):
+        raise TypeError("complex matrices are outside the MI355X path (float32/float64 only)")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"{name} needs a square matrix, not {A.shape}")
+    dt = np.dtype(A.dtype if dtype is None else dtype)
+    if dt not in (np.float32, np.float64):
+        if dtype is not None:
+            raise TypeError(f"dtype must be float32 or float64, not {dt}")
+        dt = np.dtype(np.float64)
+    csr = scipy.sparse.csr_matrix(A, dtype=dt, copy=True)
+    csr.sum_duplicates()
+    csr.sort_indices()
+    return csr, dt
+
+
+def refuse_sharded(**ops):
+    """The multi-GPU drivers take matrix preconditioners only."""
+    for name, op in ops.items():
+        for o in op if isinstance(op, (list, tuple)) else [op]:
+            if getattr(o, "factored", False):
+                raise NotImplementedError(
+                    f"{name}: a factorised preconditioner ({type(o).__name__}) runs on one device; "
+                    "krylov_amd.distributed.* and devices=[...] take matrix preconditioners only"
+                )
+
+
+class _Factored:
+    """What the drivers use on a preconditioner: shape, dtype, ctx, handle,
+    matvec_device / matvec_op, ``@``."""
+
+    factored = True
+    renumbered = False
+
+    def _setup(self, n, dt, ctx, stages):
+        self.shape = (n, n)
+        self.n = n
+        self.dtype = dt
+        self.ctx = ctx
+        self._stages = stages  # TriangularOperators and (n,) DeviceVectors, kept alive with the handle
+        h = ctypes.c_void_p()
+        check(lib.kry_precond_create(ctx.handle, n, _lib.dtype_code(dt), ctypes.byref(h)))
+        self.handle = h
+        self._fin = _lib.own(self, lib.kry_precond_destroy, h)
+        for s in stages:
+            if isinstance(s, TriangularOperator):
+                check(lib.kry_precond_add_tri(h, s.handle))
+            else:
+                check(lib.kry_precond_add_scale(h, s.handle))
+
+    @property
+    def device(self):
+        return self.ctx.device
+
+    def layout(self):
+        """{"stages": one entry per stage, a triangular solve's plan (levels,
+        launches, ...; TriangularOperator.layout) or {"scale": n}}."""
+        return {"stages": [s.layout() if isinstance(s, TriangularOperator) else {"scale": self.n}
+                           for s in self._stages]}
+
+    def matvec_device(self, x, y):
+        """y = P x for DeviceVectors (n x k, k a power of two <= 64, this
+        preconditioner's dtype) in the caller's numbering; y may be x."""
+        check(lib.kry_precond_apply(self.ctx.handle, self.handle, x.handle, y.handle))
+
+    matvec_op = matvec_device  # never renumbered
+
+    def solve(self, y):
+        """P y for a host array of shape (n,) or (n, k)."""
+        y = np.asarray(y)
+        if y.shape[0] != self.n:
+            raise ValueError("dimension mismatch")
+        y2 = np.ascontiguousarray(y.reshape(self.n, -1), dtype=self.dtype)
+        k = y2.shape[1]
+        kp = _next_pow2(k)
+        if kp > MAX_COLS:
+            raise NotImplementedError("at most 64 right-hand-side columns on a factorised preconditioner")
+        if kp != k:
+            y2 = np.concatenate([y2, np.zeros((self.n, kp - k), dtype=self.dtype)], axis=1)
+        yv = DeviceVector(self.ctx, self.n, kp, self.dtype)
+        yv.upload(y2)
+        xv = DeviceVector(self.ctx, self.n, kp, self.dtype)
+        self.matvec_device(yv, xv)
+        return np.ascontiguousarray(xv.to_host()[:, :k]).reshape(y.shape)
+
+    __matmul__ = solve
+
+    def close(self):
+        self._fin()
+
+    def __repr__(self):
+        return f"{type(self).__name__}(n={self.n}, dtype={self.dtype}, device={self.device})"
+
+
+class SsorPreconditioner(_Factored):
+    """``M = (2 - omega)/omega (D/omega + U)^-1 D (D/omega + L)^-1`` for
+    A = L + D + U (the update of the reference's ssor, stationary.py:64-94, as
+    a preconditioner). ``A``: scipy.sparse matrix or dense array; ``dtype``:
+    the dtype of the vectors it will precondition (default A's)."""
+
+    def __init__(self, A, omega=1.0, dtype=None, device=None):
+        csr, dt = _canonical(A, "SsorPreconditioner", dtype)
+        n = csr.shape[0]
+        d = csr.diagonal()
+        if n and np.any(d == 0):
+            raise np.linalg.LinAlgError(f"A has a zero or missing diagonal entry (row {int(np.argmax(d == 0))})")
+        self.omega = float(omega)
+        dw = (d / dt.type(omega)).astype(dt)
+        diag = scipy.sparse.diags(dw, format="csr", dtype=dt)
+        self._lower = (scipy.sparse.tril(csr, -1) + diag).tocsr().astype(dt)
+        self._upper = (scipy.sparse.triu(csr, 1) + diag).tocsr().astype(dt)
+        self._scale = (d * dt.type((2 - omega) / omega)).astype(dt)
+        ctx = get_context(device)
+        sv = DeviceVector.from_host(ctx, self._scale.reshape(-1, 1), dtype=dt)
+        self._setup(n, dt, ctx, [TriangularOperator(self._lower, lower=True, ctx=ctx, dtype=dt), sv,
+                                 TriangularOperator(self._upper, lower=False, ctx=ctx, dtype=dt)])
+
+    def factors(self):
+        """(D/omega + L, D/omega + U, D (2 - omega)/omega): the two triangles
+        as scipy CSR and the scale vector applied between their solves."""
+        return self._lower, self._upper, self._scale
+
+
+class Ilu0Preconditioner(_Factored):
+    """``M = U^-1 L^-1`` with the incomplete factors of A on A's own pattern,
+    factorised on the device. Every row of A must store its diagonal entry;
+    a pivot that comes out zero or non-finite raises ``LinAlgError`` naming the
+    row."""
+
+    def __init__(self, A, dtype=None, device=None):
+        csr, dt = _canonical(A, "Ilu0Preconditioner", dtype)
+        n, nnz = csr.shape[0], int(csr.nnz)
+        if nnz >= 2**31 - 1:
+            raise NotImplementedError("the ILU(0) factorisation indexes entries in int32")
+        ctx = get_context(device)
+        indptr = np.ascontiguousarray(csr.indptr, dtype=np.int32)
+        indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
+        data = np.ascontiguousarray(csr.data, dtype=dt)
+        vals = np.zeros(max(nnz, 1), dtype=dt)
+        info = np.zeros(4, dtype=np.int64)
+        t0 = time.perf_counter()
+        check(lib.kry_ilu0_factor(ctx.handle, n, nnz, _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data),
+                                  _lib.dtype_code(dt), _lib.KRY_I32, _lib.ptr(vals),
+                                  info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        vals = vals[:nnz]
+        # analysis, upload, the factorisation kernels and the values' way back (tools/bench_precond.py)
+        self.factor_seconds = time.perf_counter() - t0
+        self._plan = {"levels": int(info[0]), "launches": int(info[1]), "max_level": int(info[2])}
+        # the factorised values on A's pattern; L = strict lower part + I, U = the rest
+        self.lu = scipy.sparse.csr_matrix((vals, indices, indptr), shape=(n, n))
+        rows = np.repeat(np.arange(n, dtype=np.int32), np.diff(indptr))
+        low = indices < rows
+        eye = np.arange(n, dtype=np.int32)
+        self._L = scipy.sparse.coo_matrix(
+            (np.concatenate([vals[low], np.ones(n, dtype=dt)]),
+             (np.concatenate([rows[low], eye]), np.concatenate([indices[low], eye]))), shape=(n, n)).tocsr()
+        self._U = scipy.sparse.coo_matrix((vals[~low], (rows[~low], indices[~low])), shape=(n, n)).tocsr()
+        self._L.sort_indices()
+        self._U.sort_indices()
+        self._setup(n, dt, ctx, [TriangularOperator(self._L, lower=True, ctx=ctx, dtype=dt),
+                                 TriangularOperator(self._U, lower=False, ctx=ctx, dtype=dt)])
+
+    def factors(self):
+        """(L, U) as scipy CSR: L unit lower triangular (its diagonal stored),
+        U upper triangular with the pivots."""
+        return self._L, self._U
+
+    def layout(self):
+        """The plans of the two solves ("stages") and the factorisation's own
+        ("factor": {"levels", "launches", "max_level"})."""
+        return {"factor": dict(self._plan), **super().layout()}

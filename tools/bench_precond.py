@@ -1,0 +1,149 @@
+#!/usr/bin/env python
+"""Cost and effect of the factorised preconditioners (SsorPreconditioner,
+Ilu0Preconditioner) as one JSON line.
+
+    python tools/bench_precond.py [--out FILE] [--small]
+
+Workloads: poisson2d(1000) (SPD, 1,999 thin levels) and
+random_nonsym(2_000_000) (nonsymmetric, fat levels), b = ones. Per workload
+and preconditioner:
+  setup_s        the constructor, whole (host analysis, uploads, images)
+  factor_s       ILU(0) only: kry_ilu0_factor (analysis, upload, the
+                 factorisation kernels, the values' way back)
+  ms_per_apply   one P r on a device vector (k = 1): HIP events around a
+                 region of back-to-back applies, median of REGIONS regions
+  stages         levels / launches of every stage
+and per solver (cg on the SPD workload, gmres(30) = gmres_restarted on both)
+without a preconditioner and with each one (cg: M; gmres: Mr):
+  steps, success, wall_s   iterations and host wall time of one whole call to
+                 tol = 1e-8 (after a two-step call that loads the code objects
+                 and caches the operator's upload), capped at MAX_CG steps /
+                 MAX_CYCLES cycles
+No threshold is attached: the tool records what it measures.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+REGIONS = 5
+TOL = 1e-8
+MAX_CG = 6000
+MAX_CYCLES = 40
+RESTART = 30
+
+
+def median(v):
+    return float(np.median(np.asarray(v, dtype=np.float64)))
+
+
+def time_apply(P):
+    from krylov_amd.device import DeviceVector
+
+    y = DeviceVector.from_host(P.ctx, np.ones((P.n, 1)), dtype=P.dtype)
+    x = DeviceVector(P.ctx, P.n, 1, P.dtype)
+    for _ in range(2):
+        P.matvec_device(y, x)
+    P.ctx.synchronize()
+    reps = 5
+    ms = []
+    for _ in range(REGIONS):
+        P.ctx.timer_start()
+        for _ in range(reps):
+            P.matvec_device(y, x)
+        ms.append(P.ctx.timer_stop() / reps)
+    return median(ms), [round(m, 4) for m in ms]
+
+
+def build(name, make):
+    t0 = time.perf_counter()
+    P = make()
+    out = {"setup_s": time.perf_counter() - t0}
+    if hasattr(P, "factor_seconds"):
+        out["factor_s"] = P.factor_seconds
+    out["ms_per_apply"], out["ms_regions"] = time_apply(P)
+    lay = P.layout()
+    if "factor" in lay:
+        out["factor_plan"] = lay["factor"]
+    out["stages"] = [{k: s[k] for k in ("levels", "launches") if k in s} or s for s in lay["stages"]]
+    print(f"  {name}: setup {out['setup_s']:.2f} s, apply {out['ms_per_apply']:.3f} ms", file=sys.stderr, flush=True)
+    return P, out
+
+
+def solve_cg(A, b, M):
+    import krylov_amd
+
+    krylov_amd.cg(A, b, M=M, tol=0.0, maxiter=2)
+    t0 = time.perf_counter()
+    _, info = krylov_amd.cg(A, b, M=M, tol=TOL, maxiter=MAX_CG)
+    return {"steps": int(info.numsteps), "success": bool(info.success), "wall_s": time.perf_counter() - t0,
+            "final_relres": float(np.max(info.resnorms[-1]) / np.max(info.resnorms[0]))}
+
+
+def solve_gmres(A, b, Mr):
+    import krylov_amd
+
+    krylov_amd.gmres_restarted(A, b, restart=2, tol=0.0, max_cycles=1, Mr=Mr)
+    t0 = time.perf_counter()
+    _, infos = krylov_amd.gmres_restarted(A, b, restart=RESTART, tol=TOL, max_cycles=MAX_CYCLES, Mr=Mr)
+    wall = time.perf_counter() - t0
+    first = float(np.max(infos[0].resnorms[0]))
+    return {"steps": int(sum(i.numsteps for i in infos)), "cycles": len(infos), "success": bool(infos[-1].success),
+            "wall_s": wall, "final_relres": float(np.max(infos[-1].resnorms[-1])) / first}
+
+
+def workload(name, A, spd):
+    import krylov_amd
+
+    n = A.shape[0]
+    b = np.ones(n)
+    out = {"n": n, "nnz": int(A.nnz), "precond": {}, "solves": {}}
+    precs = {"none": None}
+    for pname, make in (("ssor", lambda: krylov_amd.SsorPreconditioner(A, omega=1.0)),
+                        ("ilu0", lambda: krylov_amd.Ilu0Preconditioner(A))):
+        try:
+            precs[pname], out["precond"][pname] = build(pname, make)
+        except Exception as e:  # recorded, not hidden: e.g. a singular pivot
+            out["precond"][pname] = {"error": f"{type(e).__name__}: {e}"}
+    solvers = ([("cg", solve_cg)] if spd else []) + [(f"gmres({RESTART})", solve_gmres)]
+    for sname, fn in solvers:
+        for pname, P in precs.items():
+            with np.errstate(all="ignore"):
+                try:
+                    r = fn(A, b, P)
+                except Exception as e:
+                    r = {"error": f"{type(e).__name__}: {e}"}
+            out["solves"][f"{sname}/{pname}"] = r
+            print(f"  {name} {sname}/{pname}: {r}", file=sys.stderr, flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--small", action="store_true", help="tiny sizes (a rehearsal of the script, not a measurement)")
+    args = ap.parse_args()
+    from krylov_amd import _lib, problems
+
+    if _lib.device_count() < 1:
+        raise SystemExit("bench_precond needs a GPU: it measures nothing without one")
+    m, n = (60, 20_000) if args.small else (1000, 2_000_000)
+    res = {"bench": "precond", "regions": REGIONS, "tol": TOL, "max_cg": MAX_CG, "max_cycles": MAX_CYCLES,
+           "restart": RESTART, "build_id": _lib.build_id(), "workloads": {}}
+    res["workloads"][f"poisson2d({m})"] = workload("poisson2d", problems.poisson2d(m), True)
+    res["workloads"][f"random_nonsym({n})"] = workload("random_nonsym", problems.random_nonsym(n), False)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
