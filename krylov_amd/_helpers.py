@@ -10,6 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._lib import check
 from .sparse import _next_pow2, as_device_operator
 
 # the reference's record (_helpers.py:93-98) plus ``renumbered``: True when
@@ -210,14 +211,18 @@ class Problem:
             return v[0]
         return v.reshape(self.tail)
 
-    def op_handles(self, *names):
-        """ctypes handles of the named preconditioners (None = identity)."""
-        return [None if self.ops[nm] is None or _is_factored(self.ops[nm]) else self.ops[nm].handle for nm in names]
-
-    def factored_slots(self, *names):
-        """(slot, handle) of the named preconditioners that are factorised
-        objects, slot = the name's position (kry_*_set_precond)."""
-        return [(i, self.ops[nm].handle) for i, nm in enumerate(names) if _is_factored(self.ops[nm])]
+    def install_preconditioners(self, set_matrices, set_factored, handle, *names):
+        """Hand the named preconditioners to a solver core: the matrices in
+        one ``kry_*_set_preconditioners`` call (None = identity, also in a
+        slot that holds a factorised object), then each factorised object
+        into its slot, the name's position (``kry_*_set_precond``)."""
+        if not self.has_precond():
+            return
+        ops = [self.ops[nm] for nm in names]
+        check(set_matrices(handle, *[None if op is None or _is_factored(op) else op.handle for op in ops]))
+        for slot, op in enumerate(ops):
+            if _is_factored(op):
+                check(set_factored(handle, slot, op.handle))
 
     def has_precond(self):
         return any(op is not None for op in self.ops.values())

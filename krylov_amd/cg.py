@@ -35,10 +35,7 @@ class _CGState:
         self._fin = _lib.own(self, lib.kry_cg_destroy, h)
         if prob.ops["Mr"] is not None:
             raise TypeError("cg has no right preconditioner Mr")
-        if prob.has_precond():
-            check(lib.kry_cg_set_preconditioners(h, *prob.op_handles("M", "Ml")))
-            for slot, ph in prob.factored_slots("M", "Ml"):
-                check(lib.kry_cg_set_precond(h, slot, ph))
+        prob.install_preconditioners(lib.kry_cg_set_preconditioners, lib.kry_cg_set_precond, h, "M", "Ml")
 
     def start(self):
         p = self.prob

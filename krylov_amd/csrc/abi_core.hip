@@ -422,19 +422,6 @@ __global__ void lartg_kernel(int64_t count, const T *f, const T *g, T *c, T *s, 
 
 }  // namespace kry
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                                                    \
-  return KRY_OK;                                                       \
-  }                                                                    \
-  catch (const kry::Error &e) {                                        \
-    kry::set_error(e.msg);                                             \
-    return e.code;                                                     \
-  }                                                                    \
-  catch (const std::exception &e) {                                    \
-    kry::set_error(e.what());                                          \
-    return KRY_EDEVICE;                                                \
-  }
-
 extern "C" {
 
 // 101: kry_csr_info_n (size-checked image info); kry_csr_info back to its
@@ -956,7 +943,7 @@ int kry_vec_create(kry_ctx *ctx, int64_t n, int32_t k, int dtype, kry_vec **out)
   v->n = n;
   v->k = k;
   v->dtype = dtype;
-  const size_t elems = ((size_t)n * k + 15) / 16 * 16;
+  const size_t elems = padded_elems(n, k);
   try {
     v->d = dev_alloc(elems * dsize(dtype));
     KRY_HIP(hipMemsetAsync(v->d, 0, elems * dsize(dtype), ctx->stream));

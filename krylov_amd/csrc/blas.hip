@@ -253,19 +253,6 @@ void check_same(const kry_vec *a, const kry_vec *b, const char *what) {
 
 }  // namespace
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
-
 extern "C" {
 
 int kry_vec_lincomb(kry_ctx *ctx, int form, kry_vec *z, kry_vec *x, kry_vec *y, kry_vec *w, const double *a,

@@ -24,29 +24,18 @@
 #include <tuple>
 #include <utility>
 
-#include "precond.hpp"
-#include "solver_common.hpp"
+#include "solver_core.hpp"
 
 using namespace kry;
 
-struct kry_cg {
-  kry_ctx *ctx = nullptr;
-  kry_csr *A = nullptr;
-  int64_t n = 0;
-  int k = 1;
-  int dtype = 0;
+// part: 2 * part_rows(k) * k; scal: the S_* slots below; sharded: gbuf holds
+// total_k + 1 (allreduced residual norms, fault count)
+struct kry_cg : SolverCore {
   bool scalar_f32 = false;
-  void *b = nullptr, *x0 = nullptr, *y = nullptr, *r = nullptr, *p = nullptr;
-  void *Ap = nullptr, *xk = nullptr, *rt = nullptr;
+  void *y = nullptr, *r = nullptr, *p = nullptr, *Ap = nullptr;
   PrecSlot M, Ml;  // preconditioners: a matrix or a kry_precond (empty = identity)
   void *z = nullptr;                    // M Ml_r (with M)
   void *t = nullptr;                    // A p / scratch (with Ml)
-  double *w = nullptr;
-  double *part = nullptr;  // 2 * part_rows(k) * k
-  double *scal = nullptr;  // scalar slots, see S_* below
-  double *hist = nullptr;  // chunk_cap * hist_k
-  Ctrl *ctrl = nullptr;
-  int chunk_cap = 0;
   int64_t it = 0;
   // deferred yk (ydefer = D > 0): the ring is indexed by the GLOBAL step
   // (p_g in pring[g % (D + 1)], alpha_g in alpha_ring[g % D]) across run
@@ -56,12 +45,6 @@ struct kry_cg {
   // kry_cg_get x, kry_cg_residual). it_base: the global step of a run's step 0
   int64_t yfb = 0;
   int64_t it_base = 0;
-  bool started = false;
-  // multi-GPU
-  kry_comm *comm = nullptr;
-  int col_offset = 0, total_k = 0;
-  double *gbuf = nullptr;  // total_k + 1 (allreduced residual norms, fault count)
-  double *gcrit = nullptr; // total_k
   // persistent small-n loop (cg_persist_kernel): its scratch r, two p
   // buffers, the y output, the scalar staging slots, barrier and granule
   // words; cgp_spw = -1 undecided, 0 not used, else slices/wave. The kernel
@@ -262,20 +245,6 @@ __global__ void cg_rho_kernel(const double *part, int P, int k, double *scal, do
   if (all_le(rn, scal + S_CRIT * k, k, &flag) && threadIdx.x == 0) ctrl->stop_at = step + 1;
 }
 
-// global stop test on the allreduced residual norms (slot total_k: the fault
-// count, post_fault)
-__global__ void cg_global_check(const double *gbuf, const double *gcrit, int total_k, double *hist, Ctrl *ctrl,
-                                int step) {
-  if (halted(ctrl, step)) return;
-  if (peer_fault(gbuf, total_k + 1, ctrl, step)) return;
-  __shared__ int flag;
-  for (int t = threadIdx.x; t < total_k; t += blockDim.x) hist[(int64_t)step * total_k + t] = gbuf[t];
-  if (all_le(gbuf, gcrit, total_k, &flag) && threadIdx.x == 0) ctrl->stop_at = step + 1;
-}
-
-// Ml r and M Ml r with <Ml r, M Ml r> partials for r = b - A src
-// (cg.py:70-90); returns the partial count. Leaves Ml r in `mlr` and M Ml r in
-// `z` (when M is set).
 // Steps 4-5 fused (no preconditioner): every block finishes <r, r> from the
 // update pass's partials in the same fixed order, derives omega, and applies
 // yk += alpha p (cg.py:196) and p = r + omega p (cg.py:178) to its span; block
@@ -1085,29 +1054,17 @@ __global__ __launch_bounds__(kCgpBlock) void cg_persist_kernel(
   }
 }
 
+// Ml r -> mlr and M Ml r -> z (when M is set) for r = b - A src, the raw
+// residual in `raw` under Ml (cg.py:70-90)
 template <typename V, typename MV, typename I>
 int cg_residual_chain(kry_cg *s, const V *src, V *raw, V *mlr) {
-  hipStream_t st = s->ctx->stream;
-  const int k = s->k;
-  int P = 0;
-  const V *bb = static_cast<const V *>(s->b);
-  if (!s->Ml && !s->M) {
-    launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiResidual<V>{bb, mlr, s->w, k}, s->part, &P, nullptr, 0,
-                          st);
-    return P;
-  }
-  if (s->Ml) {
-    launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiResidual<V>{bb, raw, s->w, k}, s->part, &P, nullptr, 0,
-                          st);
-    apply_prec<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
-  } else {
-    launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiResidual<V>{bb, mlr, s->w, k}, s->part, &P, nullptr, 0,
-                          st);
-  }
-  if (s->M)
-    apply_prec<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->z), mlr, s->w, k}, s->part,
-                       &P, nullptr, 0, st);
-  return P;
+  return residual_chain<V, MV, I>(s, s->Ml, s->M, src, raw, mlr, static_cast<V *>(s->z));
+}
+
+// the scratch each preconditioner slot needs: 0 = M, 1 = Ml
+SlotDesc cg_slot(kry_cg *s, int slot) {
+  if (slot == 0) return {&s->M, {{&s->z, vec_bytes(s)}}};
+  return {&s->Ml, {{&s->t, vec_bytes(s)}}};
 }
 
 template <typename V, typename MV, typename I>
@@ -1193,7 +1150,7 @@ bool cgp_launch_t(kry_cg *s, int max_steps, bool decide_only) {
         break;
       }
       if (s->cgp_spw > 0) {
-        const size_t vb = ((size_t)s->n + 15) / 16 * 16 * sizeof(V);
+        const size_t vb = vec_bytes(s);  // k = 1 here
         s->rs = dev_alloc(vb);
         s->pb = dev_alloc(vb);
         s->pb2 = dev_alloc(vb);
@@ -1447,7 +1404,7 @@ static void cg_ydefer_setup(kry_cg *s) {
   if (s->ydefer < 0) {
     s->ydefer = 0;
     const char *e = getenv("KRY_CG_YDEFER");
-    const size_t vb = ((size_t)s->n * k + 15) / 16 * 16 * dsize(s->dtype);
+    const size_t vb = vec_bytes(s);
     size_t fr = 0, tot = 0;
     KRY_HIP(hipMemGetInfo(&fr, &tot));
     // the default: only for vectors larger than half the 256 MB MALL (a
@@ -1593,15 +1550,7 @@ bool cg_run_impl(kry_cg *s, int max_steps) {
         launch_elementwise<V>(N, k, OpCgP<V>{p, zv, s->scal + S_OMEGA * k, k}, nullptr, s->ctrl, step, st);
       }
     }
-    if (s->comm) {
-      // exactly one collective per iteration: the residual-norm vector and the
-      // fault count (post_fault)
-      inject_peer_fault(s->gbuf, s->total_k + 1, step, st);
-      comm_allreduce(s->comm, s->gbuf, s->total_k + 1, st);
-      hipLaunchKernelGGL(cg_global_check, dim3(1), dim3(kBlock), 0, st, s->gbuf, s->gcrit, s->total_k, s->hist,
-                         s->ctrl, step);
-      KRY_HIP(hipGetLastError());
-    }
+    if (s->comm) global_step<false>(s, step);  // the residual-norm vector and the fault count (post_fault)
   }
   return false;  // (deferred yk: the updates pending now wait for cg_ydefer_flush)
 }
@@ -1634,27 +1583,10 @@ void cg_residual_impl(kry_cg *s, double *norm2) {
   // explicit ||M Ml (b - A xk)||: t and z are free between iterations
   V *mlr = static_cast<V *>(s->Ml ? s->t : s->rt);
   const int P = cg_residual_chain<V, MV, I>(s, static_cast<const V *>(s->xk), static_cast<V *>(s->rt), mlr);
-  double *out = s->scal + S_TMP * k;
-  hipLaunchKernelGGL(reduce_to_kernel<0>, dim3(1), dim3(kBlock), 0, st, s->part, P, k, out);
-  KRY_HIP(hipGetLastError());
-  KRY_HIP(hipMemcpyAsync(norm2, out, k * 8, hipMemcpyDeviceToHost, st));
-  KRY_HIP(hipStreamSynchronize(st));
+  residual_out(s, P, S_TMP, norm2);
 }
 
 }  // namespace
-
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
 
 static void cg_free(kry_cg *s) {
   void *bufs[] = {s->b,    s->x0,   s->y,     s->r,    s->p,    s->Ap,       s->z,
@@ -1669,27 +1601,15 @@ extern "C" {
 
 int kry_cg_create(kry_ctx *ctx, kry_csr *A, int32_t k, int dtype, kry_cg **out) {
   KRY_API_BEGIN
-  KRY_REQUIRE(ctx && A && out, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(is_pow2(k) && k <= kMaxCols, KRY_EUNSUPPORTED, "k must be a power of two <= 256");
-  KRY_REQUIRE(dtype == A->dtype || (dtype == KRY_F64 && A->dtype == KRY_F32), KRY_EINVAL,
-              "vectors must have the operator dtype (or float64 over a float32 operator)");
+  check_create(ctx, A, out, k, dtype);
   KRY_HIP(hipSetDevice(ctx->device));
   auto *s = new kry_cg();
   try {
-    s->ctx = ctx;
-    s->A = A;
-    s->n = A->n;
-    s->k = k;
-    s->dtype = dtype;
-    const size_t vb = ((size_t)A->n * k + 15) / 16 * 16 * dsize(dtype);
+    init_core(s, ctx, A, k, dtype);
     void **vecs[] = {&s->b, &s->y, &s->r, &s->p, &s->Ap, &s->xk, &s->rt};
-    for (void **v : vecs) {
-      *v = dev_alloc(vb);
-      KRY_HIP(hipMemsetAsync(*v, 0, vb, ctx->stream));
-    }
+    for (void **v : vecs) *v = alloc_zeroed(vec_bytes(s), ctx->stream);
     s->part = static_cast<double *>(dev_alloc(2 * part_rows(k) * k * 8));
-    s->scal = static_cast<double *>(dev_alloc(S_COUNT * (size_t)k * 8));
-    KRY_HIP(hipMemsetAsync(s->scal, 0, S_COUNT * (size_t)k * 8, ctx->stream));
+    s->scal = static_cast<double *>(alloc_zeroed(S_COUNT * (size_t)k * 8, ctx->stream));
     s->chunk_cap = 64;
     s->hist = static_cast<double *>(dev_alloc((size_t)s->chunk_cap * k * 8));
     s->ctrl = static_cast<Ctrl *>(dev_alloc(sizeof(Ctrl)));
@@ -1717,27 +1637,9 @@ int kry_cg_destroy(kry_cg *s) {
 int kry_cg_start(kry_cg *s, kry_vec *b, kry_vec *x0, kry_vec *w, double *rho0) {
   KRY_API_BEGIN
   KRY_REQUIRE(s && rho0, KRY_EINVAL, "null argument");
-  check_vec(b, s->n, s->k, s->dtype, "b");
-  if (x0) check_vec(x0, s->n, s->k, s->dtype, "x0");
-  check_weights(w, s->n);
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  hipStream_t st = s->ctx->stream;
+  check_start(s, b, x0, w);
+  hipStream_t st = load_start(s, b, x0, w);
   const size_t vb = b->bytes();
-  // b, x0 and the weights arrive in the caller's numbering (load_in: into a
-  // renumbered operator's, a plain copy otherwise)
-  load_in(s->A, b->d, s->b, s->k, dsize(s->dtype), st);
-  dev_free(s->x0);
-  s->x0 = nullptr;
-  if (x0) {
-    s->x0 = dev_alloc(((size_t)s->n * s->k + 15) / 16 * 16 * dsize(s->dtype));
-    load_in(s->A, x0->d, s->x0, s->k, dsize(s->dtype), st);
-  }
-  dev_free(s->w);
-  s->w = nullptr;
-  if (w) {
-    s->w = static_cast<double *>(dev_alloc(((size_t)s->n + 1) * 8));
-    load_in(s->A, w->d, s->w, 1, 8, st);
-  }
   // the inner product's dtype: float32 for an unweighted fp32 solve (np.dot of
   // float32), float64 otherwise (weights are float64)
   s->scalar_f32 = (s->dtype == KRY_F32 && !w);
@@ -1758,14 +1660,7 @@ int kry_cg_start(kry_cg *s, kry_vec *b, kry_vec *x0, kry_vec *w, double *rho0) {
 
 int kry_cg_set_criterion(kry_cg *s, const double *criterion) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && criterion, KRY_EINVAL, "null argument");
-  hipStream_t st = s->ctx->stream;
-  if (s->comm) {
-    KRY_HIP(hipMemcpyAsync(s->gcrit, criterion, s->total_k * 8, hipMemcpyHostToDevice, st));
-  } else {
-    KRY_HIP(hipMemcpyAsync(s->scal + S_CRIT * s->k, criterion, s->k * 8, hipMemcpyHostToDevice, st));
-  }
-  KRY_HIP(hipStreamSynchronize(st));
+  set_criterion(s, criterion, S_CRIT);
   KRY_API_END
 }
 
@@ -1775,13 +1670,8 @@ int kry_cg_run(kry_cg *s, int32_t max_steps, int32_t *steps_done, double *resnor
   KRY_REQUIRE(s->started, KRY_EINVAL, "kry_cg_start has not been called");
   KRY_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->ctx->stream;
-  const int hk = s->comm ? s->total_k : s->k;
-  if (max_steps > s->chunk_cap) {
-    dev_free(s->hist);
-    s->hist = nullptr;
-    s->hist = static_cast<double *>(dev_alloc((size_t)max_steps * hk * 8));
-    s->chunk_cap = max_steps;
-  }
+  const int hk = hist_cols(s);
+  grow_hist(s, max_steps);
   auto run_steps = [&](int steps, double *rows, Ctrl *c) -> std::pair<int, bool> {
     reset_ctrl(s->ctrl, st);
     bool persistent = false;
@@ -1932,69 +1822,23 @@ int kry_cg_scalars(kry_cg *s, double *out) {
 int kry_cg_set_preconditioners(kry_cg *s, kry_csr *M, kry_csr *Ml) {
   KRY_API_BEGIN
   KRY_REQUIRE(s, KRY_EINVAL, "null solver");
-  for (kry_csr *op : {M, Ml}) {
-    if (!op) continue;
-    KRY_REQUIRE(op->n == s->n, KRY_EINVAL, "preconditioner shape does not match the operator");
-    KRY_REQUIRE(op->dtype == s->dtype || (s->dtype == KRY_F64 && op->dtype == KRY_F32), KRY_EINVAL,
-                "preconditioner dtype must match the vectors (or be float32 under float64 vectors)");
-    KRY_REQUIRE(op->renumbered == s->A->renumbered && op->perm_hash == s->A->perm_hash, KRY_EINVAL,
-                "preconditioner renumbered differently from the operator (build it with kry_csr_create_like)");
-  }
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  const size_t vb = ((size_t)s->n * s->k + 15) / 16 * 16 * dsize(s->dtype);
-  s->M = M;
-  s->Ml = Ml;
-  if (M && !s->z) {
-    s->z = dev_alloc(vb);
-    KRY_HIP(hipMemsetAsync(s->z, 0, vb, s->ctx->stream));
-  }
-  if (Ml && !s->t) {
-    s->t = dev_alloc(vb);
-    KRY_HIP(hipMemsetAsync(s->t, 0, vb, s->ctx->stream));
-  }
-  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
-  s->started = false;
+  kry_csr *const ops[] = {M, Ml};
+  check_matrices(s, ops);
+  install_matrices(s, ops, [&](int i) { return cg_slot(s, i); });
   KRY_API_END
 }
 
 // slot 0 = M, 1 = Ml: a factorised preconditioner in place of the slot's matrix
 int kry_cg_set_precond(kry_cg *s, int32_t slot, const kry_precond *P) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && P, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(slot == 0 || slot == 1, KRY_EINVAL, "slot must be 0 (M) or 1 (Ml)");
-  precond_check(P, s->A, s->n, s->k, s->dtype);
-  KRY_REQUIRE(!s->comm, KRY_EUNSUPPORTED, "factorised preconditioners do not run on sharded solves");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  const size_t vb = ((size_t)s->n * s->k + 15) / 16 * 16 * dsize(s->dtype);
-  void *&buf = slot == 0 ? s->z : s->t;
-  if (!buf) {
-    buf = dev_alloc(vb);
-    KRY_HIP(hipMemsetAsync(buf, 0, vb, s->ctx->stream));
-    KRY_HIP(hipStreamSynchronize(s->ctx->stream));
-  }
-  (slot == 0 ? s->M : s->Ml) = P;
-  s->started = false;
+  check_factored(s, slot, 2, P);
+  install_factored(s, cg_slot(s, slot), P);
   KRY_API_END
 }
 
 int kry_cg_attach_comm(kry_cg *s, kry_comm *c, int32_t col_offset, int32_t total_k) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && c, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(col_offset >= 0 && total_k >= col_offset + s->k && total_k <= 4096, KRY_EINVAL,
-              "bad column range");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  dev_free(s->gbuf);
-  dev_free(s->gcrit);
-  s->gbuf = nullptr;
-  s->gcrit = nullptr;
-  s->gbuf = static_cast<double *>(dev_alloc(((size_t)total_k + 1) * 8));  // + the fault count
-  s->gcrit = static_cast<double *>(dev_alloc((size_t)total_k * 8));
-  dev_free(s->hist);
-  s->hist = nullptr;
-  s->hist = static_cast<double *>(dev_alloc((size_t)s->chunk_cap * total_k * 8));
-  s->comm = c;
-  s->col_offset = col_offset;
-  s->total_k = total_k;
+  attach_comm(s, c, col_offset, total_k, 1);  // + the fault count
   KRY_API_END
 }
 

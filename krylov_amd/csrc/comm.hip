@@ -7,19 +7,6 @@
 
 using namespace kry;
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
-
 #define KRY_NCCL(call)                                                                         \
   do {                                                                                         \
     ncclResult_t r_ = (call);                                                                  \

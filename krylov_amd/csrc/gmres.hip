@@ -15,21 +15,19 @@
 //             (arnoldi.py:185-189, gmres.py:206-221)
 //   normalise V_{k+1} = w / guard(h[k+1])                       arnoldi.py:191-196
 // All scalars stay on the device; the host sees the residual-norm history.
-#include "precond.hpp"
-#include "solver_common.hpp"
+#include "solver_core.hpp"
 
 using namespace kry;
 
-struct kry_gmres {
-  kry_ctx *ctx = nullptr;
-  kry_csr *A = nullptr;
-  int64_t n = 0;
-  int k = 1;
-  int dtype = 0;
+// scal: alpha[k], hsafe[k], crit[k], tmp[k]; part, part1, part2: partial rows
+// (MGS ping-pong); sharded (kry_gmres_attach_comm): one allreduce per step of
+// the zero-padded residual-norm vector + a non-invariant count + the fault
+// count (gbuf: total_k + 2), global stop
+struct kry_gmres : SolverCore {
   int maxiter = 0;
   int sweeps = 1;
   size_t vstride = 0;  // elements per basis vector (padded)
-  void *b = nullptr, *x0 = nullptr, *V = nullptr, *wv = nullptr, *xk = nullptr, *rt = nullptr;
+  void *V = nullptr, *wv = nullptr;
   PrecSlot M, Ml, Mr;  // preconditioners: a matrix or a kry_precond (empty = identity)
   void *P = nullptr;    // (maxiter + 1) basis vectors P_j (with M; else P = V)
   void *mw = nullptr;   // M w (with M)
@@ -46,26 +44,16 @@ struct kry_gmres {
   void *U = nullptr;      // (maxiter + 2) vectors
   void *vnew = nullptr;   // the next basis vector under construction
   double *hh = nullptr;   // (maxiter + 2) x HH_COUNT
-  double *w = nullptr;
-  double *part = nullptr, *part1 = nullptr, *part2 = nullptr;  // partial rows (MGS ping-pong)
-  double *scal = nullptr;  // alpha[k], hsafe[k], crit[k], tmp[k]
+  double *part1 = nullptr, *part2 = nullptr;
   double *h = nullptr;     // (maxiter + 2) x k, current Arnoldi column
   double *R = nullptr;     // (maxiter + 1) x maxiter x k
   double *Hs = nullptr;    // (maxiter + 1) x maxiter x k: the Hessenberg columns before rotation
   double *y = nullptr;     // (maxiter + 1) x k
   double *Gc = nullptr, *Gs = nullptr;  // maxiter x k rotations
   double *yy = nullptr;    // maxiter x k triangular-solve result
-  double *hist = nullptr;
-  Ctrl *ctrl = nullptr;
   // grid-barrier words of the persistent MGS kernel: 16 per chunk step,
   // zeroed once per chunk (kry_gmres_run)
   unsigned *bar = nullptr;
-  // RHS sharding (kry_gmres_attach_comm): one allreduce per step of the
-  // zero-padded residual-norm vector + a non-invariant count, global stop
-  kry_comm *comm = nullptr;
-  double *gbuf = nullptr;   // total_k + 2 (norms, non-invariant count, fault count)
-  double *gcrit = nullptr;  // total_k
-  int col_offset = 0, total_k = 0;
   int mgsp_E = -1;  // persistent MGS: -1 undecided, 0 not used, else elements per thread
   const void *mgsp_kern = nullptr;  // the kernel chosen with mgsp_E (mgsp_launch, once per solver)
   bool mgsp_streamed = false;  // it is a gm_mgsl_kernel (basis streamed, normalising)
@@ -76,10 +64,8 @@ struct kry_gmres {
   unsigned long long *mgs_tbuf = nullptr;  // KRY_MGS_TRACE phase sums (256 blocks x 4)
   int64_t mgs_tpasses = 0;
   int mgs_tgrid = 0;
-  int chunk_cap = 0;
   int steps = 0;           // Arnoldi iterations done (arnoldi.iter)
   bool invariant = false;
-  bool started = false;
   bool have_solution = false;
 };
 
@@ -1145,7 +1131,7 @@ __global__ void gm_qr_kernel(const double *part, int P, int k, double *scal, dou
     if (!gbuf) hist[(int64_t)step * k + c] = rn[c];
   }
   __syncthreads();
-  if (gbuf) {  // sharded: this rank's share of the global vector; gm_global_check decides
+  if (gbuf) {  // sharded: this rank's share of the global vector; global_check_kernel decides
     for (int t = threadIdx.x; t < total_k; t += blockDim.x) {
       const int lc = t - col_offset;
       gbuf[t] = (lc >= 0 && lc < k) ? rn[lc] : 0.0;
@@ -1157,23 +1143,6 @@ __global__ void gm_qr_kernel(const double *part, int P, int k, double *scal, dou
     return;
   }
   const bool conv = all_le(rn, scal + G_CRIT * k, k, &flag);
-  if (threadIdx.x == 0) {
-    if (inv) ctrl->invariant = 1;
-    if (inv || conv) ctrl->stop_at = step + 1;
-  }
-}
-
-// Sharded global step decision on the allreduced vector: the history row,
-// np.all(h[k+1] <= 1e-14) over ALL columns of all ranks (arnoldi.py:187) and
-// the stop rule over all columns (gmres.py:193).
-__global__ void gm_global_check(const double *gbuf, const double *gcrit, int total_k, double *hist, Ctrl *ctrl,
-                                int step) {
-  if (halted(ctrl, step)) return;
-  if (peer_fault(gbuf, total_k + 2, ctrl, step)) return;
-  __shared__ int flag;
-  for (int t = threadIdx.x; t < total_k; t += blockDim.x) hist[(int64_t)step * total_k + t] = gbuf[t];
-  const bool inv = gbuf[total_k] == 0.0;
-  const bool conv = all_le(gbuf, gcrit, total_k, &flag);
   if (threadIdx.x == 0) {
     if (inv) ctrl->invariant = 1;
     if (inv || conv) ctrl->stop_at = step + 1;
@@ -1439,42 +1408,18 @@ struct OpSuffixSq {  // partials of <x[off:], x[off:]> (householder.py:32)
   }
 };
 
-// w = Ml (A (Mr v)) (Product(Ml, A, Mr), gmres.py:139), `epi` on the last product.
-template <typename V, typename MV, typename I, class Epi>
-void gm_apply_op(kry_gmres *s, const V *v, Epi epi, double *part, int *P, const Ctrl *ctrl, int step) {
-  hipStream_t st = s->ctx->stream;
-  const int k = s->k;
-  const V *src = v;
-  if (s->Mr) {
-    V *t1 = static_cast<V *>(s->t1);
-    apply_prec<V>(s->Mr, k, SrcPlain<V>{v, k}, EpiStore<V>{t1, k}, nullptr, nullptr, ctrl, step, st);
-    src = t1;
-  }
-  if (s->Ml) {
-    V *t2 = static_cast<V *>(s->t2);
-    launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiStore<V>{t2, k}, nullptr, nullptr, ctrl, step, st);
-    apply_prec<V>(s->Ml, k, SrcPlain<V>{t2, k}, epi, part, P, ctrl, step, st);
-  } else {
-    launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, epi, part, P, ctrl, step, st);
-  }
-}
-
-// Ml (b - A z) -> mlr, M Ml (b - A z) -> mw (with M), and the partials of
-// <Ml r, M Ml r> (gmres.py:111-118); returns the partial count.
+// Ml (b - A z) -> mlr, M Ml (b - A z) -> mw (with M); the raw residual in t2
 template <typename V, typename MV, typename I>
 int gm_residual_chain(kry_gmres *s, const V *z, V *mlr) {
-  hipStream_t st = s->ctx->stream;
-  const int k = s->k;
-  int P = 0;
-  V *raw = s->Ml ? static_cast<V *>(s->t2) : mlr;
-  launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{z, k}, EpiResidual<V>{static_cast<const V *>(s->b), raw, s->w, k},
-                        s->part, &P, nullptr, 0, st);
-  if (s->Ml)
-    apply_prec<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
-  if (s->M)
-    apply_prec<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), mlr, s->w, k},
-                       s->part, &P, nullptr, 0, st);
-  return P;
+  return residual_chain<V, MV, I>(s, s->Ml, s->M, z, static_cast<V *>(s->t2), mlr, static_cast<V *>(s->mw));
+}
+
+// the scratch each preconditioner slot needs: 0 = M, 1 = Ml, 2 = Mr
+SlotDesc gm_slot(kry_gmres *s, int slot) {
+  const size_t vb = vec_bytes(s);
+  if (slot == 0) return {&s->M, {{&s->P, vb * ((size_t)s->maxiter + 1)}, {&s->mw, vb}}};
+  if (slot == 1) return {&s->Ml, {{&s->t2, vb}}};
+  return {&s->Mr, {{&s->t1, vb}}};
 }
 
 template <typename V, typename MV, typename I>
@@ -1521,7 +1466,7 @@ void hh_run_impl(kry_gmres *s, int max_steps) {
     int P;
     {
       ProfScope ps(s->ctx, PROF_SPMV);  // Av = A V_k with <U_0, Av> partials
-      gm_apply_op<V, MV, I>(s, basis<V>(s->V, s->vstride, (int)k), EpiStoreDot<V>{w, U(0), nullptr, 1}, s->part, &P,
+      apply_op<V, MV, I>(s, basis<V>(s->V, s->vstride, (int)k), EpiStoreDot<V>{w, U(0), nullptr, 1}, s->part, &P,
                             s->ctrl, step);
     }
     hipLaunchKernelGGL(reduce_to_kernel<0>, dim3(1), dim3(kBlock), 0, st, s->part, P, 1, s->part1);
@@ -1728,12 +1673,7 @@ void gm_qr_step(kry_gmres *s, const double *pin, int P, int col, int step) {
                      s->Gs, col, s->maxiter, s->hist, s->ctrl, step, 0, s->comm ? s->gbuf : nullptr, s->col_offset,
                      s->total_k, s->Hs);
   KRY_HIP(hipGetLastError());
-  if (!s->comm) return;
-  inject_peer_fault(s->gbuf, s->total_k + 2, step, st);
-  comm_allreduce(s->comm, s->gbuf, s->total_k + 2, st);
-  hipLaunchKernelGGL(gm_global_check, dim3(1), dim3(kBlock), 0, st, (const double *)s->gbuf,
-                     (const double *)s->gcrit, s->total_k, s->hist, s->ctrl, step);
-  KRY_HIP(hipGetLastError());
+  if (s->comm) global_step<true>(s, step);
 }
 
 template <typename V, typename MV, typename I>
@@ -1762,7 +1702,7 @@ void gm_run_impl(kry_gmres *s, int max_steps) {
         s->vpending = false;
       } else {
         w = wb[s->wcur];
-        gm_apply_op<V, MV, I>(s, Vk, EpiStoreDot<V>{w, V0, s->w, k}, s->part, &P, s->ctrl, step);
+        apply_op<V, MV, I>(s, Vk, EpiStoreDot<V>{w, V0, s->w, k}, s->part, &P, s->ctrl, step);
       }
     }
     if (fuse_norm && !s->w && mgsp_launch<V>(s, w, s->part, P, col, step)) {
@@ -1866,14 +1806,8 @@ void gm_solution_impl(kry_gmres *s) {
 
 template <typename V, typename MV, typename I>
 void gm_residual_impl(kry_gmres *s, double *norm2) {
-  hipStream_t st = s->ctx->stream;
-  const int k = s->k;
   const int P = gm_residual_chain<V, MV, I>(s, static_cast<const V *>(s->xk), static_cast<V *>(s->rt));
-  double *out = s->scal + G_TMP * k;
-  hipLaunchKernelGGL(reduce_to_kernel<0>, dim3(1), dim3(kBlock), 0, st, s->part, P, k, out);
-  KRY_HIP(hipGetLastError());
-  KRY_HIP(hipMemcpyAsync(norm2, out, k * 8, hipMemcpyDeviceToHost, st));
-  KRY_HIP(hipStreamSynchronize(st));
+  residual_out(s, P, G_TMP, norm2);
 }
 
 void gm_free(kry_gmres *s) {
@@ -1885,42 +1819,22 @@ void gm_free(kry_gmres *s) {
 
 }  // namespace
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
-
 extern "C" {
 
 int kry_gmres_create(kry_ctx *ctx, kry_csr *A, int32_t k, int dtype, int32_t maxiter, int32_t sweeps,
                      kry_gmres **out) {
   KRY_API_BEGIN
-  KRY_REQUIRE(ctx && A && out, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(is_pow2(k) && k <= kMaxCols, KRY_EUNSUPPORTED, "k must be a power of two <= 256");
-  KRY_REQUIRE(dtype == A->dtype || (dtype == KRY_F64 && A->dtype == KRY_F32), KRY_EINVAL,
-              "vectors must have the operator dtype (or float64 over a float32 operator)");
+  check_create(ctx, A, out, k, dtype);
   KRY_REQUIRE(maxiter >= 0 && sweeps >= 0, KRY_EINVAL, "bad maxiter / sweeps");
   KRY_REQUIRE(sweeps >= 1 || k == 1, KRY_EUNSUPPORTED, "Householder Arnoldi works on one right-hand side");
   KRY_HIP(hipSetDevice(ctx->device));
   auto *s = new kry_gmres();
   try {
-    s->ctx = ctx;
-    s->A = A;
-    s->n = A->n;
-    s->k = k;
-    s->dtype = dtype;
+    init_core(s, ctx, A, k, dtype);
     s->maxiter = maxiter;
     s->sweeps = sweeps;
-    s->vstride = ((size_t)A->n * k + 15) / 16 * 16;
-    const size_t vb = s->vstride * dsize(dtype);
+    s->vstride = vec_elems(s);
+    const size_t vb = vec_bytes(s);
     s->b = dev_alloc(vb);
     s->wv = dev_alloc(vb);
     s->wv2 = dev_alloc(vb);
@@ -1965,66 +1879,19 @@ int kry_gmres_create(kry_ctx *ctx, kry_csr *A, int32_t k, int dtype, int32_t max
 int kry_gmres_set_preconditioners(kry_gmres *s, kry_csr *M, kry_csr *Ml, kry_csr *Mr) {
   KRY_API_BEGIN
   KRY_REQUIRE(s, KRY_EINVAL, "null solver");
-  for (kry_csr *op : {M, Ml, Mr}) {
-    if (!op) continue;
-    KRY_REQUIRE(op->n == s->n, KRY_EINVAL, "preconditioner shape does not match the operator");
-    KRY_REQUIRE(op->dtype == s->dtype || (s->dtype == KRY_F64 && op->dtype == KRY_F32), KRY_EINVAL,
-                "preconditioner dtype must match the vectors (or be float32 under float64 vectors)");
-    KRY_REQUIRE(op->renumbered == s->A->renumbered && op->perm_hash == s->A->perm_hash, KRY_EINVAL,
-                "preconditioner renumbered differently from the operator (build it with kry_csr_create_like)");
-  }
+  kry_csr *const ops[] = {M, Ml, Mr};
+  check_matrices(s, ops);
   KRY_REQUIRE(!(M && s->householder), KRY_EINVAL, "Householder Arnoldi does not take M (gmres.py:160)");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  const size_t vb = s->vstride * dsize(s->dtype);
-  auto need = [&](void *&buf, size_t bytes) {
-    if (!buf) {
-      buf = dev_alloc(bytes);
-      KRY_HIP(hipMemsetAsync(buf, 0, bytes, s->ctx->stream));
-    }
-  };
-  s->M = M;
-  s->Ml = Ml;
-  s->Mr = Mr;
-  if (M) {
-    need(s->P, vb * ((size_t)s->maxiter + 1));
-    need(s->mw, vb);
-  }
-  if (Mr) need(s->t1, vb);
-  if (Ml) need(s->t2, vb);
-  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
-  s->started = false;
+  install_matrices(s, ops, [&](int i) { return gm_slot(s, i); });
   KRY_API_END
 }
 
 // slot 0 = M, 1 = Ml, 2 = Mr: a factorised preconditioner in place of the slot's matrix
 int kry_gmres_set_precond(kry_gmres *s, int32_t slot, const kry_precond *P) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && P, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(slot >= 0 && slot <= 2, KRY_EINVAL, "slot must be 0 (M), 1 (Ml) or 2 (Mr)");
-  precond_check(P, s->A, s->n, s->k, s->dtype);
-  KRY_REQUIRE(!s->comm, KRY_EUNSUPPORTED, "factorised preconditioners do not run on sharded solves");
+  check_factored(s, slot, 3, P);
   KRY_REQUIRE(!(slot == 0 && s->householder), KRY_EINVAL, "Householder Arnoldi does not take M (gmres.py:160)");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  const size_t vb = s->vstride * dsize(s->dtype);
-  auto need = [&](void *&buf, size_t bytes) {
-    if (!buf) {
-      buf = dev_alloc(bytes);
-      KRY_HIP(hipMemsetAsync(buf, 0, bytes, s->ctx->stream));
-    }
-  };
-  if (slot == 0) {
-    need(s->P, vb * ((size_t)s->maxiter + 1));
-    need(s->mw, vb);
-    s->M = P;
-  } else if (slot == 1) {
-    need(s->t2, vb);
-    s->Ml = P;
-  } else {
-    need(s->t1, vb);
-    s->Mr = P;
-  }
-  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
-  s->started = false;
+  install_factored(s, gm_slot(s, slot), P);
   KRY_API_END
 }
 
@@ -2055,29 +1922,11 @@ int kry_gmres_destroy(kry_gmres *s) {
 int kry_gmres_start(kry_gmres *s, kry_vec *b, kry_vec *x0, kry_vec *w, double *r0norm) {
   KRY_API_BEGIN
   KRY_REQUIRE(s && r0norm, KRY_EINVAL, "null argument");
-  check_vec(b, s->n, s->k, s->dtype, "b");
-  if (x0) check_vec(x0, s->n, s->k, s->dtype, "x0");
-  check_weights(w, s->n);
+  check_start(s, b, x0, w);
   KRY_REQUIRE(!(w && s->householder), KRY_EINVAL, "Householder Arnoldi needs the Euclidean inner product");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  hipStream_t st = s->ctx->stream;
+  hipStream_t st = load_start(s, b, x0, w);
   const size_t vb = b->bytes();
   const int k = s->k;
-  // b, x0 and the weights arrive in the caller's numbering (load_in: into a
-  // renumbered operator's, a plain copy otherwise)
-  load_in(s->A, b->d, s->b, k, dsize(s->dtype), st);
-  dev_free(s->x0);
-  s->x0 = nullptr;
-  if (x0) {
-    s->x0 = dev_alloc(s->vstride * dsize(s->dtype));
-    load_in(s->A, x0->d, s->x0, k, dsize(s->dtype), st);
-  }
-  dev_free(s->w);
-  s->w = nullptr;
-  if (w) {
-    s->w = static_cast<double *>(dev_alloc(((size_t)s->n + 1) * 8));
-    load_in(s->A, w->d, s->w, 1, 8, st);
-  }
   const size_t m1 = (size_t)s->maxiter + 1;
   KRY_HIP(hipMemsetAsync(s->xk, 0, vb, st));
   KRY_HIP(hipMemsetAsync(s->R, 0, m1 * (s->maxiter > 0 ? s->maxiter : 1) * k * 8, st));
@@ -2099,12 +1948,7 @@ int kry_gmres_start(kry_gmres *s, kry_vec *b, kry_vec *x0, kry_vec *w, double *r
 
 int kry_gmres_set_criterion(kry_gmres *s, const double *criterion) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && criterion, KRY_EINVAL, "null argument");
-  if (s->comm)  // all total_k columns, in rank order
-    KRY_HIP(hipMemcpyAsync(s->gcrit, criterion, s->total_k * 8, hipMemcpyHostToDevice, s->ctx->stream));
-  else
-    KRY_HIP(hipMemcpyAsync(s->scal + G_CRIT * s->k, criterion, s->k * 8, hipMemcpyHostToDevice, s->ctx->stream));
-  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
+  set_criterion(s, criterion, G_CRIT);
   KRY_API_END
 }
 
@@ -2117,16 +1961,13 @@ int kry_gmres_run(kry_gmres *s, int32_t max_steps, int32_t *steps_done, double *
   KRY_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->ctx->stream;
   if (max_steps > s->maxiter - s->steps) max_steps = s->maxiter - s->steps;
-  if (max_steps > s->chunk_cap) {
-    dev_free(s->hist);
-    s->hist = nullptr;
-    s->hist = static_cast<double *>(dev_alloc((size_t)max_steps * (s->comm ? s->total_k : s->k) * 8));
+  if (max_steps > s->chunk_cap) {  // the barrier words grow with the history
     dev_free(s->bar);
     s->bar = nullptr;
     s->bar = static_cast<unsigned *>(dev_alloc(bar_bytes(max_steps)));
-    s->chunk_cap = max_steps;
   }
-  const int hk = s->comm ? s->total_k : s->k;
+  grow_hist(s, max_steps);
+  const int hk = hist_cols(s);
   auto run_chunk = [&](int steps, double *rows, Ctrl *c) {
     reset_ctrl(s->ctrl, st);
     dispatch_vmi(s->dtype, s->A->dtype, s->A->itype, [&](auto v0, auto m0, auto i0) { gm_run_impl<decltype(v0), decltype(m0), decltype(i0)>(s, steps); });
@@ -2270,23 +2111,8 @@ int kry_gmres_get(kry_gmres *s, int which, void *host) {
 // returned by kry_gmres_run then hold total_k values.
 int kry_gmres_attach_comm(kry_gmres *s, kry_comm *c, int32_t col_offset, int32_t total_k) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && c, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(col_offset >= 0 && total_k >= col_offset + s->k && total_k <= 4096, KRY_EINVAL,
-              "bad column range");
-  KRY_REQUIRE(!s->householder, KRY_EUNSUPPORTED, "Householder Arnoldi is single right-hand side");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  dev_free(s->gbuf);
-  dev_free(s->gcrit);
-  s->gbuf = nullptr;
-  s->gcrit = nullptr;
-  s->gbuf = static_cast<double *>(dev_alloc(((size_t)total_k + 2) * 8));  // + non-invariant and fault counts
-  s->gcrit = static_cast<double *>(dev_alloc((size_t)total_k * 8));
-  dev_free(s->hist);
-  s->hist = nullptr;
-  s->hist = static_cast<double *>(dev_alloc((size_t)s->chunk_cap * total_k * 8));
-  s->comm = c;
-  s->col_offset = col_offset;
-  s->total_k = total_k;
+  attach_comm(s, c, col_offset, total_k, 2,  // + non-invariant and fault counts
+              s && s->householder ? "Householder Arnoldi is single right-hand side" : nullptr);
   KRY_API_END
 }
 

@@ -1,11 +1,13 @@
 // Host-only plumbing shared by the HIP translation units and the plain C++
 // one (host_image.cpp, which the sanitizer builds compile on their own):
-// image geometry constants, the error type and KRY_REQUIRE.
+// image geometry constants, the error type, KRY_REQUIRE and the
+// KRY_API_BEGIN / KRY_API_END frame of the exported functions.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
+#include <exception>
 #include <string>
 
 #include "../../include/krylov_hip.h"
@@ -42,3 +44,18 @@ struct Error {
   } while (0)
 
 }  // namespace kry
+
+// The body of every extern "C" entry point sits between these two: an Error
+// becomes its code and message (kry_last_error), anything else KRY_EDEVICE.
+#define KRY_API_BEGIN try {
+#define KRY_API_END                  \
+  return KRY_OK;                     \
+  }                                  \
+  catch (const kry::Error &e) {      \
+    kry::set_error(e.msg);           \
+    return e.code;                   \
+  }                                  \
+  catch (const std::exception &e) {  \
+    kry::set_error(e.what());        \
+    return KRY_EDEVICE;              \
+  }

@@ -1028,19 +1028,6 @@ template void release_later<uint32_t>(hvec<uint32_t> &);
 
 using namespace kry;
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
-
 template <typename I>
 static void rs_plan_host(int64_t n, int64_t nnz, const I *ip, const I *ix, int64_t *info, int32_t *widths,
                          uint32_t *colrank) {

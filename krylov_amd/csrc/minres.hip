@@ -17,40 +17,23 @@
 // Precision follows the reference under NumPy-2 promotion: Lanczos scalars
 // in the vector dtype, the inner products in the inner's dtype, R / rotations
 // / y / z / W in float64 (minres.py:195, 219).
-#include "precond.hpp"
-#include "solver_common.hpp"
+#include "solver_core.hpp"
 
 using namespace kry;
 
-struct kry_minres {
-  kry_ctx *ctx = nullptr;
-  kry_csr *A = nullptr;
-  int64_t n = 0;
-  int k = 1;
-  int dtype = 0;
+struct kry_minres : SolverCore {
   bool inner_f32 = false;  // inner products in float32 (unweighted fp32)
-  void *b = nullptr, *x0 = nullptr, *yk = nullptr, *wv = nullptr, *xk = nullptr, *rt = nullptr;
+  void *yk = nullptr, *wv = nullptr;
   void *P[3] = {nullptr, nullptr, nullptr};  // ring: p_old, p (= v), p_new
   double *W[2] = {nullptr, nullptr};         // float64 W ring
   PrecSlot M, Ml, Mr;  // preconditioners: a matrix or a kry_precond (empty = identity)
   void *Vr[2] = {nullptr, nullptr};  // v = M p ring (with M; else v = p)
   void *mw = nullptr;                // M w (with M)
   void *t1 = nullptr, *t2 = nullptr; // Mr v (with Mr), A Mr v / raw residual (with Ml)
-  double *w = nullptr;
-  double *part = nullptr;
-  double *scal = nullptr;
-  double *hist = nullptr;
-  Ctrl *ctrl = nullptr;
-  // RHS sharding (kry_minres_attach_comm), as in GMRES
-  kry_comm *comm = nullptr;
-  double *gbuf = nullptr;   // total_k + 2 (norms, non-invariant count, fault count)
-  double *gcrit = nullptr;  // total_k
-  int col_offset = 0, total_k = 0;
-  int chunk_cap = 0;
+  // sharded: gbuf holds total_k + 2 (norms, non-invariant count, fault count)
   int64_t it = 0;
   int wflip = 0;
   bool invariant = false;
-  bool started = false;
   // one-launch update (mr_upd_kernel): upd_nv = -1 undecided, 0 not used,
   // else granules per thread; its abort word and granule region
   int upd_nv = -1;
@@ -248,7 +231,7 @@ __global__ void mr_qr_kernel(const double *part, int P, int k, double *scal, int
     if (!gbuf) hist[(int64_t)step * k + c] = rn[c];
   }
   __syncthreads();
-  if (gbuf) {  // sharded: this rank's share of the global vector; mr_global_check decides
+  if (gbuf) {  // sharded: this rank's share of the global vector; global_check_kernel decides
     for (int t = threadIdx.x; t < total_k; t += blockDim.x) {
       const int lc = t - col_offset;
       gbuf[t] = (lc >= 0 && lc < k) ? rn[lc] : 0.0;
@@ -477,58 +460,18 @@ void *mru_kern() {
   return reinterpret_cast<void *>(mr_upd_kernel<WT, NV>);
 }
 
-// Sharded global step decision (Lanczos invariance over all columns,
-// arnoldi.py:270-272; stop rule over all columns, minres.py:162).
-__global__ void mr_global_check(const double *gbuf, const double *gcrit, int total_k, double *hist, Ctrl *ctrl,
-                                int step) {
-  if (halted(ctrl, step)) return;
-  if (peer_fault(gbuf, total_k + 2, ctrl, step)) return;
-  __shared__ int flag;
-  for (int t = threadIdx.x; t < total_k; t += blockDim.x) hist[(int64_t)step * total_k + t] = gbuf[t];
-  const bool inv = gbuf[total_k] == 0.0;
-  const bool conv = all_le(gbuf, gcrit, total_k, &flag);
-  if (threadIdx.x == 0) {
-    if (inv) ctrl->invariant = 1;
-    if (inv || conv) ctrl->stop_at = step + 1;
-  }
-}
-
-// w = Ml (A (Mr v)) (Product(Ml, A, Mr), minres.py:151), `epi` on the last product.
-template <typename V, typename MV, typename I, class Epi>
-void mr_apply_op(kry_minres *s, const V *v, Epi epi, double *part, int *P, const Ctrl *ctrl, int step) {
-  hipStream_t st = s->ctx->stream;
-  const int k = s->k;
-  const V *src = v;
-  if (s->Mr) {
-    V *t1 = static_cast<V *>(s->t1);
-    apply_prec<V>(s->Mr, k, SrcPlain<V>{v, k}, EpiStore<V>{t1, k}, nullptr, nullptr, ctrl, step, st);
-    src = t1;
-  }
-  if (s->Ml) {
-    V *t2 = static_cast<V *>(s->t2);
-    launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, EpiStore<V>{t2, k}, nullptr, nullptr, ctrl, step, st);
-    apply_prec<V>(s->Ml, k, SrcPlain<V>{t2, k}, epi, part, P, ctrl, step, st);
-  } else {
-    launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{src, k}, epi, part, P, ctrl, step, st);
-  }
-}
-
-// Ml (b - A z) -> mlr, M Ml (b - A z) -> mw (with M), partials of
-// <Ml r, M Ml r> (minres.py:105-118, 131-136); returns the partial count.
+// Ml (b - A z) -> mlr, M Ml (b - A z) -> mw (with M); the raw residual in t2
 template <typename V, typename MV, typename I>
 int mr_residual_chain(kry_minres *s, const V *z, V *mlr) {
-  hipStream_t st = s->ctx->stream;
-  const int k = s->k;
-  int P = 0;
-  V *raw = s->Ml ? static_cast<V *>(s->t2) : mlr;
-  launch_spmv<V, MV, I>(s->A, k, SrcPlain<V>{z, k}, EpiResidual<V>{static_cast<const V *>(s->b), raw, s->w, k},
-                        s->part, &P, nullptr, 0, st);
-  if (s->Ml)
-    apply_prec<V>(s->Ml, k, SrcPlain<V>{raw, k}, EpiStoreNorm<V>{mlr, s->w, k}, s->part, &P, nullptr, 0, st);
-  if (s->M)
-    apply_prec<V>(s->M, k, SrcPlain<V>{mlr, k}, EpiStoreDot<V>{static_cast<V *>(s->mw), mlr, s->w, k},
-                       s->part, &P, nullptr, 0, st);
-  return P;
+  return residual_chain<V, MV, I>(s, s->Ml, s->M, z, static_cast<V *>(s->t2), mlr, static_cast<V *>(s->mw));
+}
+
+// the scratch each preconditioner slot needs: 0 = M, 1 = Ml, 2 = Mr
+SlotDesc mr_slot(kry_minres *s, int slot) {
+  const size_t vb = vec_bytes(s);
+  if (slot == 0) return {&s->M, {{&s->Vr[0], vb}, {&s->Vr[1], vb}, {&s->mw, vb}}};
+  if (slot == 1) return {&s->Ml, {{&s->t2, vb}}};
+  return {&s->Mr, {{&s->t1, vb}}};
 }
 
 // xk = x0 + Mr yk (minres.py:95-98)
@@ -658,18 +601,12 @@ void mr_run_typed(kry_minres *s, int max_steps) {
     int PA, PB;
     {
       ProfScope ps(s->ctx, PROF_SPMV);
-      mr_apply_op<V, MV, I>(s, v, EpiLanczos<V>{w, v, pold, s->scal + M_H0 * k, s->w, k}, partA, &PA, s->ctrl, step);
+      apply_op<V, MV, I>(s, v, EpiLanczos<V>{w, v, pold, s->scal + M_H0 * k, s->w, k}, partA, &PA, s->ctrl, step);
     }
     const int f = (s->wflip + step) & 1;
     if constexpr (std::is_same<V, double>::value) {
       if (mru_launch(s, w, p, s->W[f], s->W[f ^ 1], pnew, partA, PA, step, i)) {
-        if (s->comm) {  // one collective per iteration: residual norms + non-invariant count
-          inject_peer_fault(s->gbuf, s->total_k + 2, step, st);
-          comm_allreduce(s->comm, s->gbuf, s->total_k + 2, st);
-          hipLaunchKernelGGL(mr_global_check, dim3(1), dim3(kBlock), 0, st, (const double *)s->gbuf,
-                             (const double *)s->gcrit, s->total_k, s->hist, s->ctrl, step);
-          KRY_HIP(hipGetLastError());
-        }
+        if (s->comm) global_step<true>(s, step);  // residual norms + non-invariant count
         continue;
       }
     }
@@ -683,13 +620,7 @@ void mr_run_typed(kry_minres *s, int max_steps) {
                        i >= 2 ? 1 : 0, s->hist, s->ctrl, step, s->comm ? s->gbuf : nullptr, s->col_offset,
                        s->total_k);
     KRY_HIP(hipGetLastError());
-    if (s->comm) {  // one collective per iteration: residual norms + non-invariant count
-      inject_peer_fault(s->gbuf, s->total_k + 2, step, st);
-      comm_allreduce(s->comm, s->gbuf, s->total_k + 2, st);
-      hipLaunchKernelGGL(mr_global_check, dim3(1), dim3(kBlock), 0, st, (const double *)s->gbuf,
-                         (const double *)s->gcrit, s->total_k, s->hist, s->ctrl, step);
-      KRY_HIP(hipGetLastError());
-    }
+    if (s->comm) global_step<true>(s, step);  // residual norms + non-invariant count
     {
       ProfScope ps(s->ctx, PROF_UPDATE);
       launch_elementwise<V>(N, k,
@@ -715,15 +646,9 @@ void mr_run_impl(kry_minres *s, int max_steps) {
 
 template <typename V, typename MV, typename I>
 void mr_residual_impl(kry_minres *s, double *norm2) {
-  hipStream_t st = s->ctx->stream;
-  const int k = s->k;
   mr_compute_xk<V>(s);
   const int P = mr_residual_chain<V, MV, I>(s, static_cast<const V *>(s->xk), static_cast<V *>(s->rt));
-  double *out = s->scal + M_TMP * k;
-  hipLaunchKernelGGL(reduce_to_kernel<0>, dim3(1), dim3(kBlock), 0, st, s->part, P, k, out);
-  KRY_HIP(hipGetLastError());
-  KRY_HIP(hipMemcpyAsync(norm2, out, k * 8, hipMemcpyDeviceToHost, st));
-  KRY_HIP(hipStreamSynchronize(st));
+  residual_out(s, P, M_TMP, norm2);
 }
 
 void mr_free(kry_minres *s) {
@@ -735,49 +660,20 @@ void mr_free(kry_minres *s) {
 
 }  // namespace
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
-
 extern "C" {
 
 int kry_minres_create(kry_ctx *ctx, kry_csr *A, int32_t k, int dtype, kry_minres **out) {
   KRY_API_BEGIN
-  KRY_REQUIRE(ctx && A && out, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(is_pow2(k) && k <= kMaxCols, KRY_EUNSUPPORTED, "k must be a power of two <= 256");
-  KRY_REQUIRE(dtype == A->dtype || (dtype == KRY_F64 && A->dtype == KRY_F32), KRY_EINVAL,
-              "vectors must have the operator dtype (or float64 over a float32 operator)");
+  check_create(ctx, A, out, k, dtype);
   KRY_HIP(hipSetDevice(ctx->device));
   auto *s = new kry_minres();
   try {
-    s->ctx = ctx;
-    s->A = A;
-    s->n = A->n;
-    s->k = k;
-    s->dtype = dtype;
-    const size_t elems = ((size_t)A->n * k + 15) / 16 * 16;
-    const size_t vb = elems * dsize(dtype);
+    init_core(s, ctx, A, k, dtype);
     void **vecs[] = {&s->b, &s->yk, &s->wv, &s->xk, &s->rt, &s->P[0], &s->P[1], &s->P[2]};
-    for (void **v : vecs) {
-      *v = dev_alloc(vb);
-      KRY_HIP(hipMemsetAsync(*v, 0, vb, ctx->stream));
-    }
-    for (int i = 0; i < 2; ++i) {
-      s->W[i] = static_cast<double *>(dev_alloc(elems * 8));
-      KRY_HIP(hipMemsetAsync(s->W[i], 0, elems * 8, ctx->stream));
-    }
+    for (void **v : vecs) *v = alloc_zeroed(vec_bytes(s), ctx->stream);
+    for (int i = 0; i < 2; ++i) s->W[i] = static_cast<double *>(alloc_zeroed(vec_elems(s) * 8, ctx->stream));
     s->part = static_cast<double *>(dev_alloc(2 * part_rows(k) * k * 8));
-    s->scal = static_cast<double *>(dev_alloc(M_COUNT * (size_t)k * 8));
-    KRY_HIP(hipMemsetAsync(s->scal, 0, M_COUNT * (size_t)k * 8, ctx->stream));
+    s->scal = static_cast<double *>(alloc_zeroed(M_COUNT * (size_t)k * 8, ctx->stream));
     s->chunk_cap = 64;
     s->hist = static_cast<double *>(dev_alloc((size_t)s->chunk_cap * k * 8));
     s->ctrl = static_cast<Ctrl *>(dev_alloc(sizeof(Ctrl)));
@@ -794,66 +690,17 @@ int kry_minres_create(kry_ctx *ctx, kry_csr *A, int32_t k, int dtype, kry_minres
 int kry_minres_set_preconditioners(kry_minres *s, kry_csr *M, kry_csr *Ml, kry_csr *Mr) {
   KRY_API_BEGIN
   KRY_REQUIRE(s, KRY_EINVAL, "null solver");
-  for (kry_csr *op : {M, Ml, Mr}) {
-    if (!op) continue;
-    KRY_REQUIRE(op->n == s->n, KRY_EINVAL, "preconditioner shape does not match the operator");
-    KRY_REQUIRE(op->dtype == s->dtype || (s->dtype == KRY_F64 && op->dtype == KRY_F32), KRY_EINVAL,
-                "preconditioner dtype must match the vectors (or be float32 under float64 vectors)");
-    KRY_REQUIRE(op->renumbered == s->A->renumbered && op->perm_hash == s->A->perm_hash, KRY_EINVAL,
-                "preconditioner renumbered differently from the operator (build it with kry_csr_create_like)");
-  }
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  const size_t vb = ((size_t)s->n * s->k + 15) / 16 * 16 * dsize(s->dtype);
-  auto need = [&](void *&buf) {
-    if (!buf) {
-      buf = dev_alloc(vb);
-      KRY_HIP(hipMemsetAsync(buf, 0, vb, s->ctx->stream));
-    }
-  };
-  s->M = M;
-  s->Ml = Ml;
-  s->Mr = Mr;
-  if (M) {
-    need(s->Vr[0]);
-    need(s->Vr[1]);
-    need(s->mw);
-  }
-  if (Mr) need(s->t1);
-  if (Ml) need(s->t2);
-  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
-  s->started = false;
+  kry_csr *const ops[] = {M, Ml, Mr};
+  check_matrices(s, ops);
+  install_matrices(s, ops, [&](int i) { return mr_slot(s, i); });
   KRY_API_END
 }
 
 // slot 0 = M, 1 = Ml, 2 = Mr: a factorised preconditioner in place of the slot's matrix
 int kry_minres_set_precond(kry_minres *s, int32_t slot, const kry_precond *P) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && P, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(slot >= 0 && slot <= 2, KRY_EINVAL, "slot must be 0 (M), 1 (Ml) or 2 (Mr)");
-  precond_check(P, s->A, s->n, s->k, s->dtype);
-  KRY_REQUIRE(!s->comm, KRY_EUNSUPPORTED, "factorised preconditioners do not run on sharded solves");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  const size_t vb = ((size_t)s->n * s->k + 15) / 16 * 16 * dsize(s->dtype);
-  auto need = [&](void *&buf) {
-    if (!buf) {
-      buf = dev_alloc(vb);
-      KRY_HIP(hipMemsetAsync(buf, 0, vb, s->ctx->stream));
-    }
-  };
-  if (slot == 0) {
-    need(s->Vr[0]);
-    need(s->Vr[1]);
-    need(s->mw);
-    s->M = P;
-  } else if (slot == 1) {
-    need(s->t2);
-    s->Ml = P;
-  } else {
-    need(s->t1);
-    s->Mr = P;
-  }
-  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
-  s->started = false;
+  check_factored(s, slot, 3, P);
+  install_factored(s, mr_slot(s, slot), P);
   KRY_API_END
 }
 
@@ -870,26 +717,10 @@ int kry_minres_destroy(kry_minres *s) {
 int kry_minres_start(kry_minres *s, kry_vec *b, kry_vec *x0, kry_vec *w, double *r0norm) {
   KRY_API_BEGIN
   KRY_REQUIRE(s && r0norm, KRY_EINVAL, "null argument");
-  check_vec(b, s->n, s->k, s->dtype, "b");
-  if (x0) check_vec(x0, s->n, s->k, s->dtype, "x0");
-  check_weights(w, s->n);
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  hipStream_t st = s->ctx->stream;
-  const size_t elems = ((size_t)s->n * s->k + 15) / 16 * 16;
+  check_start(s, b, x0, w);
+  hipStream_t st = load_start(s, b, x0, w);
+  const size_t elems = vec_elems(s);
   const size_t vb = b->bytes();
-  load_in(s->A, b->d, s->b, s->k, dsize(s->dtype), st);  // the caller's numbering in
-  dev_free(s->x0);
-  s->x0 = nullptr;
-  if (x0) {
-    s->x0 = dev_alloc(elems * dsize(s->dtype));
-    load_in(s->A, x0->d, s->x0, s->k, dsize(s->dtype), st);
-  }
-  dev_free(s->w);
-  s->w = nullptr;
-  if (w) {
-    s->w = static_cast<double *>(dev_alloc(((size_t)s->n + 1) * 8));
-    load_in(s->A, w->d, s->w, 1, 8, st);
-  }
   s->inner_f32 = (s->dtype == KRY_F32 && !w);
   KRY_HIP(hipMemsetAsync(s->yk, 0, vb, st));
   KRY_HIP(hipMemsetAsync(s->xk, 0, vb, st));
@@ -907,12 +738,7 @@ int kry_minres_start(kry_minres *s, kry_vec *b, kry_vec *x0, kry_vec *w, double 
 
 int kry_minres_set_criterion(kry_minres *s, const double *criterion) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && criterion, KRY_EINVAL, "null argument");
-  if (s->comm)  // all total_k columns, in rank order
-    KRY_HIP(hipMemcpyAsync(s->gcrit, criterion, s->total_k * 8, hipMemcpyHostToDevice, s->ctx->stream));
-  else
-    KRY_HIP(hipMemcpyAsync(s->scal + M_CRIT * s->k, criterion, s->k * 8, hipMemcpyHostToDevice, s->ctx->stream));
-  KRY_HIP(hipStreamSynchronize(s->ctx->stream));
+  set_criterion(s, criterion, M_CRIT);
   KRY_API_END
 }
 
@@ -924,13 +750,8 @@ int kry_minres_run(kry_minres *s, int32_t max_steps, int32_t *steps_done, double
     throw Error{KRY_EINVARIANT, "Krylov subspace was found to be invariant in the previous iteration."};
   KRY_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->ctx->stream;
-  if (max_steps > s->chunk_cap) {
-    dev_free(s->hist);
-    s->hist = nullptr;
-    s->hist = static_cast<double *>(dev_alloc((size_t)max_steps * (s->comm ? s->total_k : s->k) * 8));
-    s->chunk_cap = max_steps;
-  }
-  const int hk = s->comm ? s->total_k : s->k;
+  grow_hist(s, max_steps);
+  const int hk = hist_cols(s);
   auto run_steps = [&](int steps, double *rows, Ctrl *c) {
     reset_ctrl(s->ctrl, st);
     s->upd_used = false;
@@ -1030,22 +851,7 @@ int kry_minres_get(kry_minres *s, int which, void *host) {
 // RHS sharding: see kry_gmres_attach_comm.
 int kry_minres_attach_comm(kry_minres *s, kry_comm *c, int32_t col_offset, int32_t total_k) {
   KRY_API_BEGIN
-  KRY_REQUIRE(s && c, KRY_EINVAL, "null argument");
-  KRY_REQUIRE(col_offset >= 0 && total_k >= col_offset + s->k && total_k <= 4096, KRY_EINVAL,
-              "bad column range");
-  KRY_HIP(hipSetDevice(s->ctx->device));
-  dev_free(s->gbuf);
-  dev_free(s->gcrit);
-  s->gbuf = nullptr;
-  s->gcrit = nullptr;
-  s->gbuf = static_cast<double *>(dev_alloc(((size_t)total_k + 2) * 8));  // + non-invariant and fault counts
-  s->gcrit = static_cast<double *>(dev_alloc((size_t)total_k * 8));
-  dev_free(s->hist);
-  s->hist = nullptr;
-  s->hist = static_cast<double *>(dev_alloc((size_t)(s->chunk_cap > 0 ? s->chunk_cap : 1) * total_k * 8));
-  s->comm = c;
-  s->col_offset = col_offset;
-  s->total_k = total_k;
+  attach_comm(s, c, col_offset, total_k, 2);  // + non-invariant and fault counts
   KRY_API_END
 }
 

@@ -147,6 +147,8 @@ namespace kry {
 
 inline size_t dsize(int dtype) { return dtype == KRY_F64 ? 8 : 4; }
 inline size_t isize(int itype) { return itype == KRY_I64 ? 8 : 4; }
+// elements allocated for an n x k vector: whole 16-element groups
+inline size_t padded_elems(int64_t n, int k) { return ((size_t)n * k + 15) / 16 * 16; }
 
 void *dev_alloc(size_t bytes);
 void dev_free(void *p);  // to the caching pool (abi_core.hip)

@@ -223,20 +223,15 @@ void precond_check(const kry_precond *P, const kry_csr *A, int64_t n, int k, int
               "(KRY_RENUMBER=0 keeps the caller's numbering)");
 }
 
-}  // namespace kry
+void precond_matrix_check(const kry_csr *op, const kry_csr *A, int64_t n, int dtype) {
+  KRY_REQUIRE(op->n == n, KRY_EINVAL, "preconditioner shape does not match the operator");
+  KRY_REQUIRE(op->dtype == dtype || (dtype == KRY_F64 && op->dtype == KRY_F32), KRY_EINVAL,
+              "preconditioner dtype must match the vectors (or be float32 under float64 vectors)");
+  KRY_REQUIRE(op->renumbered == A->renumbered && op->perm_hash == A->perm_hash, KRY_EINVAL,
+              "preconditioner renumbered differently from the operator (build it with kry_csr_create_like)");
+}
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
+}  // namespace kry
 
 extern "C" {
 

@@ -35,6 +35,8 @@ void precond_stages(const kry_precond *P, int k, const void *src, void *dst, con
                     hipStream_t st);
 // what every set_precond of the cores checks
 void precond_check(const kry_precond *P, const kry_csr *A, int64_t n, int k, int dtype);
+// what every set_preconditioners of the cores checks of a matrix it is given
+void precond_matrix_check(const kry_csr *op, const kry_csr *A, int64_t n, int dtype);
 
 // A preconditioner slot of a solver. It converts to bool like the kry_csr
 // pointer it replaces, so `!s->M` and `s->M ? a : b` see both kinds.

@@ -308,19 +308,6 @@ int rcm_order_device(kry_ctx *ctx, int64_t n, const int32_t *d_ip, const int32_t
 
 using namespace kry;
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
-
 extern "C" {
 
 int kry_rcm_device(kry_ctx *ctx, int64_t n, int64_t nnz, const int32_t *indptr, const int32_t *indices, int64_t wlimit,

@@ -204,19 +204,6 @@ void tri_shape(const kry_tri *T, int64_t *n, int *dtype) {
 
 }  // namespace kry
 
-#define KRY_API_BEGIN try {
-#define KRY_API_END                  \
-  return KRY_OK;                     \
-  }                                  \
-  catch (const kry::Error &e) {      \
-    kry::set_error(e.msg);           \
-    return e.code;                   \
-  }                                  \
-  catch (const std::exception &e) {  \
-    kry::set_error(e.what());        \
-    return KRY_EDEVICE;              \
-  }
-
 extern "C" {
 
 int kry_tri_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,

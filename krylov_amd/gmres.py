@@ -58,10 +58,7 @@ class _GmresState:
                                    int(maxiter), int(sweeps), ctypes.byref(h)))
         self.h = h
         self._fin = _lib.own(self, lib.kry_gmres_destroy, h)
-        if prob.has_precond():
-            check(lib.kry_gmres_set_preconditioners(h, *prob.op_handles("M", "Ml", "Mr")))
-            for slot, ph in prob.factored_slots("M", "Ml", "Mr"):
-                check(lib.kry_gmres_set_precond(h, slot, ph))
+        prob.install_preconditioners(lib.kry_gmres_set_preconditioners, lib.kry_gmres_set_precond, h, "M", "Ml", "Mr")
 
     def start(self, x0_dev=None):
         """r0 = b - A x0 on the device; x0 = the problem's own x0 or, for a

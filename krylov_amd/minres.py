@@ -21,10 +21,7 @@ class _MinresState:
                                     ctypes.byref(h)))
         self.h = h
         self._fin = _lib.own(self, lib.kry_minres_destroy, h)
-        if prob.has_precond():
-            check(lib.kry_minres_set_preconditioners(h, *prob.op_handles("M", "Ml", "Mr")))
-            for slot, ph in prob.factored_slots("M", "Ml", "Mr"):
-                check(lib.kry_minres_set_precond(h, slot, ph))
+        prob.install_preconditioners(lib.kry_minres_set_preconditioners, lib.kry_minres_set_precond, h, "M", "Ml", "Mr")
 
     def start(self):
         p = self.prob

@@ -14,7 +14,7 @@ quantity has ``world * kpad`` slots, rank r owning ``[r kpad, (r+1) kpad)``,
 and a zero-padded allreduce (sum) is an all-gather of it.
 
 Per step the device applies the global stop rule itself after one allreduce
-(``cg_global_check`` / ``gm_global_check`` / ``mr_global_check``); the host
+(``global_check_kernel``, csrc/solver_core.hpp); the host
 part here is everything around it: the initial norms, the criterion over the
 real columns (padded slots never block the rule: +inf), the explicit
 residual recheck, the step count and the global history.

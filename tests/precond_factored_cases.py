@@ -130,7 +130,19 @@ def device_precond(krylov_amd, A, spec, dtype):
     return krylov_amd.Ilu0Preconditioner(A, dtype=dtype)
 
 
-# name, solver, slot, preconditioner spec, problem, keyword arguments
+def slot_matrix(A, tag):
+    """A matrix preconditioner named by a tag in a case's keyword arguments:
+    ("jacobi",) = diag(1 / diag(A)), ("scaled_eye", c) = c I; scipy sparse."""
+    n = A.shape[0]
+    if tag[0] == "jacobi":
+        return scipy.sparse.diags(1.0 / A.diagonal(), format="csr")
+    if tag[0] == "scaled_eye":
+        return (tag[1] * scipy.sparse.identity(n, dtype=A.dtype)).tocsr()
+    raise ValueError(f"unknown matrix tag {tag!r}")
+
+
+# name, solver, slot, preconditioner spec, problem, keyword arguments; a tuple
+# under "M" / "Ml" / "Mr" there names a matrix for that other slot (slot_matrix)
 CASES = [
     ("cg_p40_ssor", "cg", "M", ("ssor", 1.2), "p40", {"tol": 1e-8}),
     ("cg_p40_ilu0", "cg", "M", ("ilu0",), "p40", {"tol": 1e-8}),
@@ -144,6 +156,12 @@ CASES = [
     ("cgs_r3k_m", "cgs", "M", ("ilu0",), "r3k", {"tol": 1e-10, "maxiter": 60}),
     ("cheb_p40_ssor", "chebyshev", "M", ("ssor", 1.0), "p40", {"tol": 0.0, "maxiter": 30}),
     ("f32_cg_p40_ssor", "cg", "M", ("ssor", 1.0), "p40_f32", {"tol": 1e-4}),
+    # a factorised object and a matrix in one solve
+    ("gmres_r3k_ml_fac_mr_mat", "gmres", "Ml", ("ilu0",), "r3k", {"Mr": ("jacobi",), "tol": 0.0, "maxiter": 25}),
+    ("gmres_p40_m_fac_mr_mat", "gmres", "M", ("ssor", 1.0), "p40", {"Mr": ("jacobi",), "tol": 0.0, "maxiter": 20}),
+    ("cg_p40_m_mat_ml_fac", "cg", "Ml", ("ssor", 1.0), "p40", {"M": ("jacobi",), "tol": 0.0, "maxiter": 15}),
+    ("minres_p40_m_fac_ml_mr_mat", "minres", "M", ("ssor", 1.0), "p40",
+     {"Ml": ("scaled_eye", 0.5), "Mr": ("scaled_eye", 0.5), "tol": 0.0, "maxiter": 20}),
 ]
 
 
@@ -162,8 +180,11 @@ def problem(problems, key):
 
 
 def call(mod, solver, A, b, slot, P, kw, eigs=None, **extra):
-    """mod.<solver>(A, b, ..., <slot>=P, **kw)."""
+    """mod.<solver>(A, b, ..., <slot>=P, **kw), the matrix tags in kw resolved."""
     kw = dict(kw, **extra)
+    for nm in ("M", "Ml", "Mr"):
+        if isinstance(kw.get(nm), tuple):
+            kw[nm] = slot_matrix(A, kw[nm])
     kw[slot] = P
     if solver == "chebyshev":
         return mod.chebyshev(A, b, eigs, **kw)

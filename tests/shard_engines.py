@@ -11,9 +11,9 @@ Per step an engine does what the device chunk does: the local recurrence
 (cg.py:175-209 / arnoldi.py:167-200 + gmres.py:206-221 / arnoldi.py:237-281 +
 minres.py:193-228, via the oracle's helpers), ONE allreduce of the
 zero-padded residual norms plus the number of non-invariant columns, and the
-global stop rule ``np.all(row <= criterion)`` that ``cg_global_check`` /
-``gm_global_check`` / ``mr_global_check`` apply on the device; a chunk ends
-after the first step that meets it.
+global stop rule ``np.all(row <= criterion)`` that ``global_check_kernel``
+(csrc/solver_core.hpp) applies on the device; a chunk ends after the first
+step that meets it.
 """
 import numpy as np
 

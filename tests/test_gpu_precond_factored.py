@@ -120,6 +120,51 @@ def test_callback_sees_every_iterate(fixtures):
     assert len(seen) == info.numsteps + 1
 
 
+def test_a_setter_replaces_the_slot_and_needs_a_new_start(matrices):
+    """One CG state over poisson2d(12): a factorised M, then
+    kry_cg_set_preconditioners with a matrix M (which clears the factorised
+    one), then the factorised M again through kry_cg_set_precond. After each
+    setter a run is refused until the next start, and the history then equals,
+    bitwise, a fresh solver's that was given only that M."""
+    import krylov_amd
+    from krylov_amd import _helpers
+    from krylov_amd._lib import check, lib
+    from krylov_amd.cg import _CGState
+
+    S = matrices["poisson12"]
+    A = krylov_amd.CsrOperator(S)
+    b = np.random.default_rng(5).standard_normal(S.shape[0])
+    fac = krylov_amd.SsorPreconditioner(S, omega=1.2)
+    jac = scipy.sparse.diags(1.0 / S.diagonal(), format="csr")
+    steps = 10
+
+    def fresh(M):
+        st = _CGState(_helpers.Problem(A, b, None, None, M=M))
+        st.start()
+        st.set_criterion(np.zeros(1))
+        return st
+
+    def restarted(st):
+        with pytest.raises(ValueError, match="kry_cg_start has not been called"):
+            st.run(steps)
+        st.start()
+        st.set_criterion(np.zeros(1))
+        return st.run(steps)
+
+    only_jac = fresh(jac)
+    want_jac = only_jac.run(steps)
+    want_fac = fresh(fac).run(steps)
+    assert want_jac.shape == want_fac.shape == (steps, 1)
+    assert not np.array_equal(_bits(want_jac), _bits(want_fac))
+
+    st = fresh(fac)
+    np.testing.assert_array_equal(_bits(st.run(steps)), _bits(want_fac))
+    check(lib.kry_cg_set_preconditioners(st.h, only_jac.prob.ops["M"].handle, None))
+    np.testing.assert_array_equal(_bits(restarted(st)), _bits(want_jac))
+    check(lib.kry_cg_set_precond(st.h, 0, fac.handle))
+    np.testing.assert_array_equal(_bits(restarted(st)), _bits(want_fac))
+
+
 def test_gmres_restarted_with_ml(matrices):
     import krylov_amd
 

@@ -4,8 +4,8 @@ A GPU box here has one GPU, so a real W-rank run cannot execute. What can:
 ``ShardComm.solo(r, W)`` is a 1-rank RCCL communicator (its allreduce is the
 identity) with the layout of rank r of W. The solvers then attach at column
 offset r * kpad of W * kpad global slots and run every per-step collective,
-the zero-padded global vector, the global stop rule (``cg_global_check`` /
-``gm_global_check`` / ``mr_global_check``) and ``shard.drive``'s outer loop
+the zero-padded global vector, the global stop rule (``global_check_kernel``,
+csrc/solver_core.hpp) and ``shard.drive``'s outer loop
 exactly as rank r would. The other ranks' slots stay exactly 0 (nobody posts
 them), and 0 <= their criterion, so this rank's columns must reproduce the
 unsharded device solve of the same columns BIT FOR BIT: history, step count
