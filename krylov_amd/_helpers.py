@@ -211,6 +211,11 @@ class Problem:
             return v[0]
         return v.reshape(self.tail)
 
+    def colnorms(self, sq):
+        """kpad squared norms from the device -> the reference's norms (the
+        root taken in the inner products' dtype)."""
+        return self.colvals(np.sqrt(np.asarray(sq[: self.kc]).astype(self.inner_dtype)))
+
     def install_preconditioners(self, set_matrices, set_factored, handle, *names):
         """Hand the named preconditioners to a solver core: the matrices in
         one ``kry_*_set_preconditioners`` call (None = identity, also in a

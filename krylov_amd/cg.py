@@ -13,8 +13,10 @@ import time
 
 import numpy as np
 
-from . import _helpers, _lib
+from . import _lib
 from ._helpers import Info, Problem
+from ._loop import stop_rule_loop
+from ._state import CoreState
 from .device import HostOut
 from ._lib import check, lib
 
@@ -26,34 +28,15 @@ from ._lib import check, lib
 last_timing = {}
 
 
-class _CGState:
-    def __init__(self, prob):
-        self.prob = prob
-        h = ctypes.c_void_p()
-        check(lib.kry_cg_create(prob.ctx.handle, prob.A.handle, prob.kpad, _lib.dtype_code(prob.dtype), ctypes.byref(h)))
-        self.h = h
-        self._fin = _lib.own(self, lib.kry_cg_destroy, h)
-        if prob.ops["Mr"] is not None:
-            raise TypeError("cg has no right preconditioner Mr")
-        prob.install_preconditioners(lib.kry_cg_set_preconditioners, lib.kry_cg_set_precond, h, "M", "Ml")
+class _CGState(CoreState):
+    PREFIX, PRECOND, INVARIANT = "kry_cg", ("M", "Ml"), False
 
-    def start(self):
-        p = self.prob
-        rho = np.zeros(p.kpad)
-        check(lib.kry_cg_start(self.h, p.b_dev.handle, p.x0_dev.handle if p.x0_dev else None,
-                               p.w_dev.handle if p.w_dev else None, _lib.dptr(rho)))
-        return rho
-
-    def set_criterion(self, crit):
-        crit = np.ascontiguousarray(crit, dtype=np.float64)
-        check(lib.kry_cg_set_criterion(self.h, _lib.dptr(crit)))
+    def start_norms(self):
+        return np.sqrt(self.start().astype(self.prob.inner_dtype)).astype(np.float64)
 
     def run(self, steps, ncols=None):
-        ncols = self.prob.kpad if ncols is None else ncols
-        out = np.zeros((max(steps, 1), ncols))
-        done = ctypes.c_int32()
-        check(lib.kry_cg_run(self.h, int(steps), ctypes.byref(done), _lib.dptr(out)))
-        return out[: done.value]
+        """The history rows of the steps done (CG has no invariance test)."""
+        return super().run(steps, ncols)[0]
 
     def preferred_chunk(self):
         """Iterations per run call (after start): 256 on the persistent
@@ -66,17 +49,14 @@ class _CGState:
         """(persistent, fallbacks): whether the last run chunk was one
         persistent launch, and how many chunks were rerun launch per pass
         after an in-launch exchange timed out (kry_cg_path)."""
-        info = (ctypes.c_int32 * 2)()
-        check(lib.kry_cg_path(self.h, info))
-        return bool(info[0]), int(info[1])
+        persistent, fallbacks = self._pair("path")
+        return bool(persistent), fallbacks
 
     def update_path(self):
         """(path, fallbacks) of the launch-per-pass form (kry_cg_update_path):
         path 1 (== True) = the one-launch update (k = 1), 0 (== False) =
         separate passes."""
-        info = (ctypes.c_int32 * 2)()
-        check(lib.kry_cg_update_path(self.h, info))
-        return int(info[0]), int(info[1])
+        return self._pair("update_path")
 
     def defer_info(self):
         """(D, bytes): yk updates applied D steps at a time (0 = every step)
@@ -85,19 +65,6 @@ class _CGState:
         check(lib.kry_cg_defer_info(self.h, ctypes.byref(d), ctypes.byref(nb)))
         return int(d.value), int(nb.value)
 
-    def residual_norm2(self):
-        out = np.zeros(self.prob.kpad)
-        check(lib.kry_cg_residual(self.h, _lib.dptr(out)))
-        return out
-
-    def get(self, which, out=None):
-        p = self.prob
-        if out is None:
-            out = np.empty((p.n, p.kpad), dtype=p.dtype)
-        assert out.shape == (p.n, p.kpad) and out.dtype == p.dtype and out.flags.c_contiguous
-        check(lib.kry_cg_get(self.h, which, _lib.ptr(out)))
-        return out
-
     def scalars(self):
         """[rho, rho_prev, alpha, omega] rows (kpad values each)."""
         out = np.zeros((4, self.prob.kpad))
@@ -105,8 +72,15 @@ class _CGState:
         return out
 
 
-def _norm_from_sq(prob, sq):
-    return np.sqrt(np.asarray(sq[: prob.kc]).astype(prob.inner_dtype))
+def _num_operations(k):
+    return {
+        "A": 1 + k,
+        "M": 2 + k,
+        "Ml": 2 + k,
+        "Mr": 1 + k,
+        "inner": 2 + 2 * k,
+        "axpy": 2 + 2 * k,
+    }
 
 
 def cg(A, b, M=None, Ml=None, inner=None, x0=None, tol=1e-5, atol=1.0e-15, maxiter=None,
@@ -132,56 +106,37 @@ def cg(A, b, M=None, Ml=None, inner=None, x0=None, tol=1e-5, atol=1.0e-15, maxit
     t_run = 0.0
     prob = Problem(A, b, x0, inner, M=M, Ml=Ml)
     t_prob = time.perf_counter()
-    N = prob.A.shape[0]
-    maxiter = N if maxiter is None else maxiter
+    maxiter = prob.A.shape[0] if maxiter is None else maxiter
 
     st = _CGState(prob)
     x_out = HostOut((prob.n, prob.kpad), prob.dtype)  # pages faulted in while the device iterates
-    rho0 = st.start()
+    first = prob.colnorms(st.start())
     t_start = time.perf_counter()
-    chunk = st.preferred_chunk()
-    rn0 = _norm_from_sq(prob, rho0)
     if callback is not None:
         callback(prob.x0_or_zeros(), prob.unpad_vec(st.get(1), prob.r0_dtype))
-    resnorms = [prob.colvals(rn0)]
-    criterion = np.maximum(tol * resnorms[0], atol)
+    criterion = np.maximum(tol * first, atol)
     st.set_criterion(prob.pad_cols(criterion, np.inf))
-    lanczos = _Lanczos(prob, st, resnorms[0], maxiter) if return_arnoldi else None
+    lanczos = _Lanczos(prob, st, first, maxiter) if return_arnoldi else None
 
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            # the reference's explicit residual recheck (cg.py:156-164)
-            resnorms[-1] = prob.colvals(_norm_from_sq(prob, st.residual_norm2()))
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
-        steps = 1 if (callback is not None or lanczos is not None) else min(chunk, maxiter - k)
+    def run(_k, steps):
+        nonlocal t_run
         t0 = time.perf_counter()
         hist = st.run(steps)
         t_run += time.perf_counter() - t0
-        for row in hist:
-            resnorms.append(prob.colvals(row))
-            if lanczos is not None:
-                lanczos.step(k, resnorms[-1])
-            k += 1
-        if callback is not None and len(hist):
-            callback(prob.unpad_vec(st.get(0), prob.r0_dtype), prob.unpad_vec(st.get(1), prob.r0_dtype))
+        return hist, None
+
+    success, k, resnorms = stop_rule_loop(
+        first, criterion, maxiter, run, entry=prob.colvals,
+        chunk=1 if (callback is not None or lanczos is not None) else st.preferred_chunk(),
+        recheck=lambda: prob.colnorms(st.residual_norm2()),  # the explicit residual (cg.py:156-164)
+        on_step=lanczos.step if lanczos is not None else None,
+        on_chunk=None if callback is None else lambda _k, _rn: callback(
+            prob.unpad_vec(st.get(0), prob.r0_dtype), prob.unpad_vec(st.get(1), prob.r0_dtype)))
 
     t_loop = time.perf_counter()
-    xk = prob.unpad_vec(st.get(0, out=x_out.take()), prob.r0_dtype)
+    xk = st.xk(out=x_out.take())
     t_get = time.perf_counter()
-    num_operations = {
-        "A": 1 + k,
-        "M": 2 + k,
-        "Ml": 2 + k,
-        "Mr": 1 + k,
-        "inner": 2 + 2 * k,
-        "axpy": 2 + 2 * k,
-    }
+    num_operations = _num_operations(k)
     arnoldi = lanczos.result(k) if lanczos is not None else None
     t_end = time.perf_counter()
     last_timing.update(call_ms=1e3 * (t_end - t_call), chunks_ms=1e3 * t_run, problem_ms=1e3 * (t_prob - t_call),

@@ -7,8 +7,8 @@ of a chunk of iterations runs on the device scalar chain (extra.py).
 """
 import numpy as np
 
-from ._helpers import Info, Problem
-from .extra import LC_AXPY, LC_COPY, SOP_SET, _Chain, _chunks, _Dev, _real, _start
+from ._helpers import Problem
+from .extra import LC_AXPY, LC_COPY, SOP_SET, _Chain, _Dev, _real, _run_chain, _start
 from .stationary import _check_columns
 
 
@@ -31,14 +31,12 @@ def chebyshev(A, b, eigenvalue_estimates, M=None, x0=None, inner=None, tol=1e-5,
         return np.sqrt(_real(D.dot(v, D.op("M", v))))
 
     x, r = _start(D, x0)
-    resnorms = [D.cols(norm(r))]
+    first = D.cols(norm(r))
     if callback is not None:
         callback(D.host(x), D.host(r))
     C = _Chain(D, ["alpha", "beta", "nr"])
     p, ap = D.zeros(), D.zeros()
     zt, t1 = (D.zeros(), D.zeros()) if mm else (None, None)
-    criterion = np.maximum(tol * resnorms[0], atol)
-    C.set(None, prob.pad_cols(criterion, np.inf))
 
     coef = []  # (alpha, beta) of step k, chebyshev.py:78-86
 
@@ -70,25 +68,4 @@ def chebyshev(A, b, eigenvalue_estimates, M=None, x0=None, inner=None, tol=1e-5,
         C.norm(r, t1, "nr", st, M="M" if mm else None)
         C.check("nr", st)
 
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            resnorms[-1] = D.cols(norm(D.residual(x)))
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
-        steps = _chunks(D, callback) if maxiter is None else min(_chunks(D, callback), maxiter - k)
-        C.begin()
-        for st in range(steps):
-            step(st, k + st)
-        rows, _ = C.end(steps)
-        for row in rows:
-            if callback is not None:
-                callback(D.host(x), D.host(r))
-            resnorms.append(D.cols(row))
-            k += 1
-    xk = D.host_final(x)
-    return xk if success else None, Info(success, xk, k, resnorms, renumbered=prob.A.renumbered)
+    return _run_chain(D, C, x, r, first, norm, step, tol, atol, maxiter, callback)

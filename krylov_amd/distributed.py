@@ -1,9 +1,8 @@
 """Right-hand-side sharding across GPUs.
 
 The reference is "fully blocked": a block ``b`` of shape (n, K) runs K
-independent CG recurrences whose only coupling is the stop rule
-``np.all(resnorms[-1] <= criterion)`` over all columns (cg.py:156,162). Here
-the K columns are split into equal contiguous blocks, one per process/GPU;
+independent CG recurrences whose only coupling is the stop rule over all
+columns (cg.py:156,162; ``_loop.stop_rule_loop``). Here the K columns are split into equal contiguous blocks, one per process/GPU;
 each GPU runs the whole fused CG loop on its block against a replicated copy
 of A, and every iteration performs exactly one ``ncclAllReduce`` (RCCL over
 xGMI) of the zero-padded residual-norm vector so that every rank applies the
@@ -24,7 +23,7 @@ import numpy as np
 from . import _helpers, _lib
 from ._helpers import Info, Problem
 from ._lib import check, lib
-from .cg import _CGState
+from .cg import _CGState, _num_operations as _cg_operations
 from .device import get_context
 from .precond import refuse_sharded
 from .shard import ShardLayout, drive, file_rendezvous
@@ -132,34 +131,6 @@ def _block(B):
     return B[:, None] if B.ndim == 1 else B
 
 
-class _Engine:
-    """A device solver state in the shape ``shard.drive`` expects."""
-
-    def __init__(self, st, run_fn, total, start_fn, norm2_fn):
-        self.st, self._run, self.total = st, run_fn, total
-        self._start, self._norm2 = start_fn, norm2_fn
-
-    def start_norms(self):
-        return self._start()
-
-    def set_criterion(self, crit_full):
-        self.st.set_criterion(crit_full)
-
-    def run(self, steps):
-        return self._run(steps)
-
-    def residual_norm2(self):
-        return self._norm2()
-
-
-def _run_global(lib_run, h, steps, total):
-    out = np.zeros((max(steps, 1), total))
-    done = ctypes.c_int32()
-    inv = ctypes.c_int32()
-    check(lib_run(h, int(steps), ctypes.byref(done), _lib.dptr(out), ctypes.byref(inv)))
-    return out[: done.value], bool(inv.value)
-
-
 def gather_columns(comm, lay, prob, local):
     """This rank's (n, kpad) host block -> the global (n, K) block of the real
     columns, in rank order: a zero-padded allreduce (sum) over the
@@ -210,9 +181,7 @@ def cg(A, B, comm, x0=None, tol=1e-5, atol=1.0e-15, maxiter=None, callback=None,
     lay = ShardLayout(prob.kc, prob.kpad, comm.rank, comm.world, kcs)
     maxiter = prob.A.shape[0] if maxiter is None else maxiter
     st = _CGState(prob)
-    check(lib.kry_cg_attach_comm(st.h, comm.handle, lay.off, lay.total))
-    eng = _Engine(st, lambda steps: (st.run(steps, ncols=lay.total), False), lay.total,
-                  lambda: np.sqrt(st.start().astype(prob.inner_dtype)).astype(np.float64), st.residual_norm2)
+    st.attach_comm(comm, lay)
 
     def args(_rn):
         return gather_columns(comm, lay, prob, st.get(0)), gather_columns(comm, lay, prob, st.get(1))
@@ -222,11 +191,10 @@ def cg(A, B, comm, x0=None, tol=1e-5, atol=1.0e-15, maxiter=None, callback=None,
             np.zeros((prob.n, lay.real.size), dtype=prob.r0_dtype)
         return x0g, gather_columns(comm, lay, prob, st.get(1))
 
-    success, k, resnorms = drive(eng, lay, comm.allreduce, tol, atol, maxiter, prob.inner_dtype, _helpers.CHUNK,
+    success, k, resnorms = drive(st, lay, comm.allreduce, tol, atol, maxiter, prob.inner_dtype, _helpers.CHUNK,
                                  hook=_hook(callback, first, args))
-    xk = prob.unpad_vec(st.get(0), prob.r0_dtype)
-    ops = {"A": 1 + k, "M": 2 + k, "Ml": 2 + k, "Mr": 1 + k, "inner": 2 + 2 * k, "axpy": 2 + 2 * k}
-    return xk if success else None, Info(success, xk, k, resnorms, num_operations=ops,
+    xk = st.xk()
+    return xk if success else None, Info(success, xk, k, resnorms, num_operations=_cg_operations(k),
                                          renumbered=prob.A.renumbered)
 
 
@@ -240,7 +208,7 @@ def gmres(A, B, comm, x0=None, tol=1e-5, atol=1.0e-15, maxiter=None, ortho="mgs"
     ``M``/``Ml``/``Mr``, ``inner`` and ``callback(xk, resnorm)`` as in
     ``krylov_amd.gmres`` (the callback sees the gathered global iterate).
     Returns ``(xk_local or None, Info)`` with the global history."""
-    from .gmres import _GmresState, _sweeps
+    from .gmres import _GmresState, _num_operations, _sweeps
 
     if not ortho.startswith("mgs"):
         raise NotImplementedError("the sharded path runs MGS Arnoldi (Householder is single right-hand side)")
@@ -249,11 +217,7 @@ def gmres(A, B, comm, x0=None, tol=1e-5, atol=1.0e-15, maxiter=None, ortho="mgs"
     maxiter = prob.A.shape[0] if maxiter is None else maxiter
     lay = ShardLayout(prob.kc, prob.kpad, comm.rank, comm.world, kcs)
     st = _GmresState(prob, maxiter, sweeps)
-    check(lib.kry_gmres_attach_comm(st.h, comm.handle, lay.off, lay.total))
-
-    def norm2():
-        st.solution()  # the explicit residual of x0 + V R^-1 y (gmres.py:197-199)
-        return st.residual_norm2()
+    st.attach_comm(comm, lay)
 
     def first(_rn):
         # callback(x0, Ml (b - A x0)) (gmres.py:143-144), on this rank's columns, then gathered
@@ -263,21 +227,17 @@ def gmres(A, B, comm, x0=None, tol=1e-5, atol=1.0e-15, maxiter=None, ortho="mgs"
         return gather_columns(comm, lay, prob, x0l), gather_columns(comm, lay, prob, mr)
 
     def step(rn):
-        st.solution()
+        st.solve()
         return gather_columns(comm, lay, prob, prob.pad(st.xk())), np.array(rn)
 
-    eng = _Engine(st, lambda steps: _run_global(lib.kry_gmres_run, st.h, steps, lay.total), lay.total, st.start,
-                  norm2)
-    success, k, resnorms = drive(eng, lay, comm.allreduce, tol, atol, maxiter, prob.inner_dtype, _helpers.CHUNK,
+    success, k, resnorms = drive(st, lay, comm.allreduce, tol, atol, maxiter, prob.inner_dtype, _helpers.CHUNK,
                                  hook=_hook(callback, first, step))
     if k == 0:
         xk = prob.zeros_like_b() if prob.x0 is None else prob.x0
     else:
-        st.solution()
+        st.solve()
         xk = st.xk()
-    ops = {"A": 1 + k, "M": 2 + k, "Ml": 2 + k, "Mr": 1 + k, "inner": 2 + k + k * (k + 1) / 2,
-           "axpy": 4 + 2 * k + k * (k + 1) / 2}
-    return xk if success else None, Info(success, xk, k, resnorms, num_operations=ops,
+    return xk if success else None, Info(success, xk, k, resnorms, num_operations=_num_operations(k),
                                          renumbered=prob.A.renumbered)
 
 
@@ -289,13 +249,13 @@ def minres(A, B, comm, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None
     ``M``/``Ml``/``Mr`` and ``callback(xk, resnorm)`` as in
     ``krylov_amd.minres`` (the callback sees the gathered global iterate).
     Returns ``(xk_local or None, Info)`` with the global history."""
-    from .minres import _MinresState
+    from .minres import _MinresState, _num_operations
 
     prob = _problem(A, B, x0, inner, comm, M=M, Ml=Ml, Mr=Mr)
     maxiter = prob.A.shape[0] if maxiter is None else maxiter
     lay = ShardLayout(prob.kc, prob.kpad, comm.rank, comm.world, kcs)
     st = _MinresState(prob)
-    check(lib.kry_minres_attach_comm(st.h, comm.handle, lay.off, lay.total))
+    st.attach_comm(comm, lay)
 
     def first(rn):
         x0h = prob.x0_or_zeros()
@@ -304,11 +264,8 @@ def minres(A, B, comm, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None
     def step(rn):
         return gather_columns(comm, lay, prob, prob.pad(st.xk())), np.array(rn)
 
-    eng = _Engine(st, lambda steps: _run_global(lib.kry_minres_run, st.h, steps, lay.total), lay.total, st.start,
-                  st.residual_norm2)
-    success, k, resnorms = drive(eng, lay, comm.allreduce, tol, atol, maxiter, prob.inner_dtype, _helpers.CHUNK,
+    success, k, resnorms = drive(st, lay, comm.allreduce, tol, atol, maxiter, prob.inner_dtype, _helpers.CHUNK,
                                  hook=_hook(callback, first, step))
     xk = st.xk()
-    ops = {"A": 1 + k, "M": 2 + k, "Ml": 2 + k, "Mr": 1 + k, "inner": 2 + 2 * k, "axpy": 4 + 8 * k}
-    return xk if success else None, Info(success, xk, k, resnorms, num_operations=ops,
+    return xk if success else None, Info(success, xk, k, resnorms, num_operations=_num_operations(k),
                                          renumbered=prob.A.renumbered)

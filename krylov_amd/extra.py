@@ -23,6 +23,7 @@ import numpy as np
 from . import _helpers, _lib
 from ._helpers import Info, Problem
 from ._lib import check, lib
+from ._loop import stop_rule_loop
 from .device import DeviceVector, HostOut
 
 LC_AXPY, LC_NEST_ADD, LC_NEST_SUB, LC_DIV, LC_SUB, LC_ADD, LC_COPY, LC_SCALE = range(8)
@@ -203,9 +204,36 @@ class _Chain:
         check(lib.kry_prog_check(self.h, self.r[d], mode | (self.r32 if mode == 0 else 0), st))
 
 
-def _chunks(D, callback):
-    """Iterations per chunk: one with a callback (it sees every iterate)."""
-    return 1 if callback is not None else _helpers.CHUNK
+def _run_chain(D, C, x, r, first, norm, step, tol, atol, maxiter, callback, cap=None, trim=None):
+    """What the chain drivers share after their set-up: the criterion into
+    the chain, the reference's outer loop over chunks of ``step(st, k)``
+    (chunk step ``st`` enqueues iteration k; one iteration per chunk with a
+    callback, which sees every iterate), ``callback(x, r)`` after every step,
+    the returned iterate and ``Info``. ``first``: history entry 0; ``norm``:
+    the norm of the explicit-residual recheck (None: no recheck). gcr's
+    extras: ``cap(steps)`` bounds a chunk, ``trim(k)`` runs after a chunk that
+    ended with k steps done. Returns ``(xk or None, Info)``."""
+    prob = D.prob
+    criterion = np.maximum(tol * first, atol)
+    C.set(None, prob.pad_cols(criterion, np.inf))
+
+    def run(k, steps):
+        if cap is not None:
+            steps = cap(steps)
+        C.begin()
+        for st in range(steps):
+            step(st, k + st)
+        rows, mid = C.end(steps)
+        if trim is not None:
+            trim(k + len(rows))
+        return rows, mid
+
+    success, k, resnorms = stop_rule_loop(
+        first, criterion, maxiter, run, chunk=1 if callback is not None else _helpers.CHUNK, entry=D.cols,
+        recheck=None if norm is None else lambda: D.cols(norm(D.residual(x))),
+        on_step=None if callback is None else lambda _k, _rn: callback(D.host(x), D.host(r)))
+    xk = D.host_final(x)
+    return xk if success else None, Info(success, xk, k, resnorms, renumbered=prob.A.renumbered)
 
 
 def _real(v):
@@ -244,7 +272,7 @@ def bicgstab(A, b, Ml=None, Mr=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15
     r = D.copy(r0)
     if callback is not None:
         callback(D.host(x), D.host(r))
-    resnorms = [D.cols(norm(r0))]
+    first = D.cols(norm(r0))
     C = _Chain(D, ["rho", "rho_old", "alpha", "omega", "beta", "r0v", "tt", "ts", "nh", "nr"])
     for nm in ("rho", "alpha", "omega"):
         C.set(nm, 1.0)
@@ -253,10 +281,8 @@ def bicgstab(A, b, Ml=None, Mr=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15
     ml = prob.ops["Ml"] is not None
     mr = prob.ops["Mr"] is not None
     t1, t2, t3, t4, t5 = ([D.zeros() for _ in range(5)] if (ml or mr) else [None] * 5)
-    criterion = np.maximum(tol * resnorms[0], atol)
-    C.set(None, prob.pad_cols(criterion, np.inf))
 
-    def step(st):
+    def step(st, _k):
         C.sc(SOP_COPY, "rho_old", st, a="rho")
         C.dot(r0_, r, "rho", st)  # rho = inner(r0_, r)
         C.sc(SOP_MULDIVG, "beta", st, a="rho", b="alpha", c="rho_old", e="omega")
@@ -284,32 +310,7 @@ def bicgstab(A, b, Ml=None, Mr=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15
         C.norm(r, t1 if ml else None, "nr", st, M="Ml" if ml else None)
         C.check("nr", st)
 
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            resnorms[-1] = D.cols(norm(D.residual(x)))
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
-        steps = _chunks(D, callback) if maxiter is None else min(_chunks(D, callback), maxiter - k)
-        C.begin()
-        for st in range(steps):
-            step(st)
-        rows, mid = C.end(steps)
-        for row in rows:
-            if callback is not None:
-                callback(D.host(x), D.host(r))
-            resnorms.append(D.cols(row))
-            k += 1
-        if mid is not None:  # bicgstab.py:124-127
-            resnorms[-1] = D.cols(mid)
-            success = True
-            break
-    xk = D.host_final(x)
-    return xk if success else None, Info(success, xk, k, resnorms, renumbered=prob.A.renumbered)
+    return _run_chain(D, C, x, r, first, norm, step, tol, atol, maxiter, callback)
 
 
 def cgs(A, b, M=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None, callback=None):
@@ -326,15 +327,13 @@ def cgs(A, b, M=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None,
     r = D.copy(r0)
     if callback:
         callback(D.host(x), D.host(r))
-    resnorms = [D.cols(norm(r))]
+    first = D.cols(norm(r))
     C = _Chain(D, ["rho", "rho_old", "beta", "s", "alpha", "nr"])
     C.set("rho", 1.0)
     p, q, u, v, uq, au = (D.zeros() for _ in range(6))
     t1, t2 = (D.zeros(), D.zeros()) if mm else (None, None)
-    criterion = np.maximum(tol * resnorms[0], atol)
-    C.set(None, prob.pad_cols(criterion, np.inf))
 
-    def step(st):
+    def step(st, _k):
         C.sc(SOP_COPY, "rho_old", st, a="rho")
         C.dot(rp, r, "rho", st)
         C.sc(SOP_DIVG, "beta", st, a="rho", b="rho_old")
@@ -352,28 +351,7 @@ def cgs(A, b, M=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None,
         C.norm(r, t1 if mm else None, "nr", st, M="M" if mm else None)
         C.check("nr", st)
 
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            resnorms[-1] = D.cols(norm(D.residual(x)))
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
-        steps = _chunks(D, callback) if maxiter is None else min(_chunks(D, callback), maxiter - k)
-        C.begin()
-        for st in range(steps):
-            step(st)
-        rows, _ = C.end(steps)
-        for row in rows:
-            if callback:
-                callback(D.host(x), D.host(r))
-            resnorms.append(D.cols(row))
-            k += 1
-    xk = D.host_final(x)
-    return xk if success else None, Info(success, xk, k, resnorms, renumbered=prob.A.renumbered)
+    return _run_chain(D, C, x, r, first, norm, step, tol, atol, maxiter, callback)
 
 
 def cgr(A, b, M=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None, callback=None):
@@ -394,16 +372,14 @@ def cgr(A, b, M=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None,
     Ar = D.A(r)
     C = _Chain(D, ["rAr", "rAr_old", "ApMAp", "alpha", "beta", "nr"])
     C.set("rAr", D.dot(r, Ar))
-    resnorms = [D.cols(norm(r))]
+    first = D.cols(norm(r))
     if callback is not None:
         callback(D.host(x), D.host(r))
     p = D.copy(r)
     Ap = D.copy(Ar)
     mAp = D.zeros() if prob.ops["M"] is not None else None
-    criterion = np.maximum(tol * resnorms[0], atol)
-    C.set(None, prob.pad_cols(criterion, np.inf))
 
-    def step(st):
+    def step(st, _k):
         MAp = C.apply("M", Ap, mAp, st)
         C.dot(Ap, MAp, "ApMAp", st)
         C.sc(SOP_DIVG, "alpha", st, a="rAr", b="ApMAp")
@@ -418,28 +394,7 @@ def cgr(A, b, M=None, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None,
         C.norm(r, None, "nr", st)
         C.check("nr", st)
 
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            resnorms[-1] = D.cols(norm(D.residual(x)))
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
-        steps = _chunks(D, callback) if maxiter is None else min(_chunks(D, callback), maxiter - k)
-        C.begin()
-        for st in range(steps):
-            step(st)
-        rows, _ = C.end(steps)
-        for row in rows:
-            if callback is not None:
-                callback(D.host(x), D.host(r))
-            resnorms.append(D.cols(row))
-            k += 1
-    xk = D.host_final(x)
-    return xk if success else None, Info(success, xk, k, resnorms, renumbered=prob.A.renumbered)
+    return _run_chain(D, C, x, r, first, norm, step, tol, atol, maxiter, callback)
 
 
 # gcr's basis grows by two n x k vectors per step; a chunk enqueued before its
@@ -464,11 +419,9 @@ def gcr(A, b, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None, callbac
 
     if callback is not None:
         callback(D.host(x), D.host(r))
-    resnorms = [D.cols(norm(r))]
+    first = D.cols(norm(r))
     C = _Chain(D, ["alpha", "beta", "gb", "gamma", "nr"])
     s, v = [], []
-    criterion = np.maximum(tol * resnorms[0], atol)
-    C.set(None, prob.pad_cols(criterion, np.inf))
 
     def step(st, kk):
         s.append(C.lc(LC_COPY, D.zeros(), r, st))
@@ -487,29 +440,12 @@ def gcr(A, b, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxiter=None, callbac
         C.norm(r, None, "nr", st)
         C.check("nr", st)
 
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            resnorms[-1] = D.cols(norm(D.residual(x)))
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
-        steps = _chunks(D, callback) if maxiter is None else min(_chunks(D, callback), maxiter - k)
+    def cap(steps):
         # each step appends two basis vectors before the chunk's stop is known:
         # enqueue at most _GCR_CHUNK_BYTES of them ahead of the convergence test
-        steps = max(1, min(steps, _GCR_CHUNK_BYTES // max(1, 2 * prob.n * prob.kpad * prob.dtype.itemsize)))
-        C.begin()
-        for st in range(steps):
-            step(st, k + st)
-        rows, _ = C.end(steps)
-        del s[k + len(rows):], v[k + len(rows):]  # vectors of steps the chunk's stop skipped
-        for row in rows:
-            if callback is not None:
-                callback(D.host(x), D.host(r))
-            resnorms.append(D.cols(row))
-            k += 1
-    xk = D.host_final(x)
-    return xk if success else None, Info(success, xk, k, resnorms, renumbered=prob.A.renumbered)
+        return max(1, min(steps, _GCR_CHUNK_BYTES // max(1, 2 * prob.n * prob.kpad * prob.dtype.itemsize)))
+
+    def trim(k):  # vectors of steps the chunk's stop skipped
+        del s[k:], v[k:]
+
+    return _run_chain(D, C, x, r, first, norm, step, tol, atol, maxiter, callback, cap=cap, trim=trim)

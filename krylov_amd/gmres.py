@@ -7,12 +7,12 @@ Like the reference there is no restart parameter: ``maxiter`` bounds the
 Arnoldi basis, and restarted GMRES(m) is ``gmres(..., maxiter=m)`` chained
 through ``x0`` (see ``gmres_restarted``).
 """
-import ctypes
-
 import numpy as np
 
 from . import _helpers, _lib
 from ._helpers import Info, Problem
+from ._loop import stop_rule_loop
+from ._state import CoreState
 from .device import HostOut
 from ._lib import check, lib
 
@@ -50,64 +50,45 @@ def multi_solve_triangular(A, B, device=None):
     return out.astype(res_dt).reshape([A.shape[0]] + list(A.shape[2:]))
 
 
-class _GmresState:
+class _GmresState(CoreState):
+    PREFIX, PRECOND = "kry_gmres", ("M", "Ml", "Mr")
+
     def __init__(self, prob, maxiter, sweeps):
-        self.prob = prob
-        h = ctypes.c_void_p()
-        check(lib.kry_gmres_create(prob.ctx.handle, prob.A.handle, prob.kpad, _lib.dtype_code(prob.dtype),
-                                   int(maxiter), int(sweeps), ctypes.byref(h)))
-        self.h = h
-        self._fin = _lib.own(self, lib.kry_gmres_destroy, h)
-        prob.install_preconditioners(lib.kry_gmres_set_preconditioners, lib.kry_gmres_set_precond, h, "M", "Ml", "Mr")
+        super().__init__(prob, int(maxiter), int(sweeps))
+        self._solved = False  # xk holds x0 + V R^-1 y of the steps done so far
 
     def start(self, x0_dev=None):
-        """r0 = b - A x0 on the device; x0 = the problem's own x0 or, for a
-        restart chain, ``x0_dev`` (a DeviceVector of the solve's shape)."""
-        p = self.prob
-        out = np.zeros(p.kpad)
-        x0 = x0_dev if x0_dev is not None else p.x0_dev
-        check(lib.kry_gmres_start(self.h, p.b_dev.handle, x0.handle if x0 is not None else None,
-                                  p.w_dev.handle if p.w_dev else None, _lib.dptr(out)))
-        return out
+        self._solved = False
+        return super().start(x0_dev)
 
-    def set_criterion(self, crit):
-        crit = np.ascontiguousarray(crit, dtype=np.float64)
-        check(lib.kry_gmres_set_criterion(self.h, _lib.dptr(crit)))
-
-    def run(self, steps):
-        out = np.zeros((max(steps, 1), self.prob.kpad))
-        done = ctypes.c_int32()
-        inv = ctypes.c_int32()
-        check(lib.kry_gmres_run(self.h, int(steps), ctypes.byref(done), _lib.dptr(out), ctypes.byref(inv)))
-        return out[: done.value], bool(inv.value)
+    def run(self, steps, ncols=None):
+        self._solved = False
+        return super().run(steps, ncols)
 
     def solution(self):
         check(lib.kry_gmres_solution(self.h))
+        self._solved = True
+
+    def solve(self):
+        """solution(), unless xk already holds it (with no step done it is x0)."""
+        if not self._solved:
+            self.solution()
+
+    def residual_norm2(self):
+        """The explicit residual of x0 + V R^-1 y (gmres.py:197-199)."""
+        self.solve()
+        return super().residual_norm2()
 
     def path(self):
         """(persistent, fallbacks): whether Arnoldi steps run their MGS as one
         persistent launch, and how many chunks finished launch per pass after a
         persistent MGS exchange timed out (kry_gmres_path)."""
-        info = (ctypes.c_int32 * 2)()
-        check(lib.kry_gmres_path(self.h, info))
-        return bool(info[0]), int(info[1])
-
-    def residual_norm2(self):
-        out = np.zeros(self.prob.kpad)
-        check(lib.kry_gmres_residual(self.h, _lib.dptr(out)))
-        return out
+        persistent, fallbacks = self._pair("path")
+        return bool(persistent), fallbacks
 
     def xk_into(self, vec):
         """xk (after solution()) into a DeviceVector, device to device."""
         check(lib.kry_gmres_xk_device(self.h, vec.handle))
-
-    def xk(self, out=None):
-        p = self.prob
-        if out is None:
-            out = np.empty((p.n, p.kpad), dtype=p.dtype)
-        assert out.shape == (p.n, p.kpad) and out.dtype == p.dtype and out.flags.c_contiguous
-        check(lib.kry_gmres_get(self.h, 0, _lib.ptr(out)))
-        return p.unpad_vec(out, p.r0_dtype)
 
 
 def arnoldi(A, v, maxiter, ortho="mgs", M=None, inner=None):
@@ -121,16 +102,10 @@ def arnoldi(A, v, maxiter, ortho="mgs", M=None, inner=None):
     Returns ``(V, H, P, is_invariant)``: the basis as a list of vectors
     (``V = M P``), the (steps + 1) x steps Hessenberg matrix (steps x steps
     after an invariant step), and the ``P`` basis (``P is V`` without M)."""
-    if ortho.startswith("mgs"):
-        sweeps = 1 if len(ortho) == 3 else int(ortho[3:])
-    elif ortho == "householder":
-        assert inner is None and _helpers._is_identity(M)
-        sweeps = 0
-    else:
-        raise ValueError(f"unknown ortho {ortho!r}")
     v = np.asarray(v)
     if v.ndim != 1:
         raise ValueError("arnoldi takes one start vector")
+    sweeps = _sweeps(ortho, inner, M, v)
     prob = Problem(A, v, None, inner, M=M)
     st = _GmresState(prob, maxiter, sweeps)
     st.start()
@@ -146,15 +121,13 @@ def arnoldi(A, v, maxiter, ortho="mgs", M=None, inner=None):
     n, kp = prob.n, prob.kpad
 
     def basis(which):
-        out = np.empty((max(nv, 1), n, kp), dtype=prob.dtype)
-        check(lib.kry_gmres_get(st.h, which, _lib.ptr(out)))
+        out = st.get(which, out=np.empty((max(nv, 1), n, kp), dtype=prob.dtype))
         return [out[i, :, 0].copy() for i in range(nv)]
 
     V = basis(1)
     P = basis(2) if (not _helpers._is_identity(M) and sweeps > 0) else V
     mi = max(maxiter, 1)
-    Hs = np.empty((maxiter + 1, mi, kp))
-    check(lib.kry_gmres_get(st.h, 3, _lib.ptr(Hs)))
+    Hs = st.get(3, out=np.empty((maxiter + 1, mi, kp)))
     H = Hs[: steps + 1, :steps, 0].astype(prob.dtype)
     if invariant:
         H = H[:steps]
@@ -219,8 +192,7 @@ def _cycle(prob, st, maxiter, tol, atol, callback, tol_of_r0=None, x_in=None, x_
     may be ``x_in``), and the host copy of xk is made only if ``host_x`` (else
     the returned xk is None), into ``host_out`` (a ``HostOut``) when given.
     Returns ``(success, xk, numsteps, resnorms)``."""
-    rn0 = st.start(x_in)
-    resnorms = [prob.colvals(rn0)]
+    first = prob.colvals(st.start(x_in))
 
     def host_x0():
         if x_in is None:
@@ -232,48 +204,26 @@ def _cycle(prob, st, maxiter, tol, atol, callback, tol_of_r0=None, x_in=None, x_
         x0h = host_x0()
         callback(x0h, prob.apply_host("Ml", prob.b - prob.A @ x0h))
     if tol_of_r0 is not None:
-        tol = tol_of_r0(resnorms[0])
-    criterion = np.maximum(tol * resnorms[0], atol)
+        tol = tol_of_r0(first)
+    criterion = np.maximum(tol * first, atol)
     st.set_criterion(prob.pad_cols(criterion, np.inf))
 
-    steps_done = 0
-    solved = False  # st holds x0 + V R^-1 y of the steps done so far
-    k = 0
-    success = False
+    def on_chunk(_k, rn):
+        st.solve()
+        callback(st.xk(), np.array(rn))
 
-    def solve():
-        nonlocal solved
-        if not solved:
-            st.solution()
-            solved = True
-
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            solve()  # with no step done this is x0 (the explicit residual's input)
-            resnorms[-1] = prob.colvals(np.sqrt(np.asarray(st.residual_norm2()[: prob.kc]).astype(prob.inner_dtype)))
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
-        steps = 1 if callback is not None else min(_helpers.CHUNK, maxiter - k)
-        hist, _ = st.run(steps)
-        solved = False
-        for row in hist:
-            resnorms.append(prob.colvals(row))
-            k += 1
-            steps_done += 1
-        if callback is not None and len(hist):
-            solve()
-            callback(st.xk(), np.array(resnorms[-1]))
+    success, k, resnorms = stop_rule_loop(
+        first, criterion, maxiter, lambda _k, steps: (st.run(steps)[0], None), entry=prob.colvals,
+        chunk=1 if callback is not None else _helpers.CHUNK, recheck=lambda: prob.colnorms(st.residual_norm2()),
+        on_chunk=None if callback is None else on_chunk)
 
     if x_out is not None:
-        solve()
+        st.solve()
         st.xk_into(x_out)
-    if steps_done == 0:
+    if k == 0:
         xk = host_x0() if host_x else None
     else:
-        solve()
+        st.solve()
         xk = st.xk(out=host_out.take() if host_out is not None else None) if host_x else None
     return success, xk, k, resnorms
 

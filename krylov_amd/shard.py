@@ -5,8 +5,8 @@ so the same code runs over RCCL on GPUs (``krylov_amd.distributed``) and over
 gloo in the CPU tests (``tests/test_sharding_cpu.py``).
 
 The reference is fully blocked: K columns run K independent recurrences,
-coupled only by ``np.all(resnorms[-1] <= criterion)`` over ALL columns
-(``cg.py:156,162``, ``gmres.py:193``, ``minres.py:162``) and, for the
+coupled only by the stop rule over ALL columns (``cg.py:156,162``,
+``gmres.py:193``, ``minres.py:162``; ``_loop.stop_rule_loop``) and, for the
 Arnoldi/Lanczos methods, the invariance test ``np.all(h[k+1] <= 1e-14)``
 (``arnoldi.py:187``, ``arnoldi.py:270-272``). Each rank holds ``kc`` real
 columns padded to ``kpad`` on its device; the global vector of a per-column
@@ -23,6 +23,8 @@ import os
 import time
 
 import numpy as np
+
+from ._loop import stop_rule_loop
 
 
 class ShardLayout:
@@ -75,9 +77,10 @@ def drive(engine, layout, allreduce, tol, atol, maxiter, inner_dtype, chunk=32, 
     ``engine`` is this rank's solver state:
       start_norms()      -> local kpad initial residual norms (float64)
       set_criterion(v)   -> the global criterion vector (layout.total)
-      run(steps)         -> (rows, invariant): the global history rows
-                            (done x layout.total) of a chunk that stops itself
-                            after the first step meeting the global rule
+      run(steps)         -> (rows, invariant), or rows alone: the global
+                            history rows (done x layout.total) of a chunk that
+                            stops itself after the first step meeting the
+                            global rule
       residual_norm2()   -> local kpad squared explicit residual norms
     Returns ``(success, numsteps, resnorms)`` with the global history over the
     real columns, identical on every rank."""
@@ -86,36 +89,26 @@ def drive(engine, layout, allreduce, tol, atol, maxiter, inner_dtype, chunk=32, 
     def cast(v):
         return np.asarray(v, dtype=np.float64).astype(inner_dtype).astype(np.float64)
 
-    rn0 = layout.glob(engine.start_norms(), allreduce)
-    resnorms = [cast(rn0[real])]
-    criterion = np.maximum(tol * resnorms[0], atol)
+    first = cast(layout.glob(engine.start_norms(), allreduce)[real])
+    criterion = np.maximum(tol * first, atol)
     engine.set_criterion(layout.criterion_full(criterion))
     if hook is not None:
-        hook(0, resnorms[0])
+        hook(0, first)
         chunk = 1
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):
-            sq = layout.glob(engine.residual_norm2(), allreduce)
-            resnorms[-1] = np.sqrt(sq[real].astype(inner_dtype)).astype(np.float64)
-            if np.all(resnorms[-1] <= criterion):
-                success = True
-                break
-        if k == maxiter:
-            break
+
+    def run(_k, steps):
         # an invariant step is not a stop by itself (the reference's drivers
         # do not test it either: its residual meets the rule, or the next
         # Arnoldi/Lanczos step raises)
-        rows, _ = engine.run(min(chunk, maxiter - k))
-        if len(rows) == 0:
-            raise RuntimeError("sharded solve: a chunk made no progress")
-        for row in rows:
-            resnorms.append(cast(np.asarray(row)[real]))
-            k += 1
-        if hook is not None:
-            hook(k, resnorms[-1])
-    return success, k, resnorms
+        out = engine.run(steps)
+        return (out[0] if isinstance(out, tuple) else out), None
+
+    def recheck():
+        sq = layout.glob(engine.residual_norm2(), allreduce)
+        return np.sqrt(sq[real].astype(inner_dtype)).astype(np.float64)
+
+    return stop_rule_loop(first, criterion, maxiter, run, chunk=chunk, entry=lambda row: cast(np.asarray(row)[real]),
+                          recheck=recheck, on_chunk=hook)
 
 
 # ------------------------------------------------------------ rendezvous
@@ -134,14 +127,15 @@ def file_rendezvous(path, rank, payload_fn, timeout=120.0, poll=0.02):
         os.replace(tmp, path)
         return data
     t0 = time.monotonic()
-    while True:
+    data = b""
+    while not data:
         try:
             with open(path, "rb") as f:
                 data = f.read()
-            if data:
-                return data
         except FileNotFoundError:
             pass
-        if time.monotonic() - t0 > timeout:
-            raise TimeoutError(f"rank {rank}: no communicator id at {path} after {timeout:.0f} s")
-        time.sleep(poll)
+        if not data:
+            if time.monotonic() - t0 > timeout:
+                raise TimeoutError(f"rank {rank}: no communicator id at {path} after {timeout:.0f} s")
+            time.sleep(poll)
+    return data

@@ -12,9 +12,9 @@ they and jacobi refuse an operator the device renumbered at upload
 import numpy as np
 import scipy.sparse
 
-from ._helpers import Info, Problem
+from ._helpers import Problem
 from .device import DeviceVector
-from .extra import LC_ADD, LC_AXPY, LC_SUB, _Chain, _chunks, _Dev, _real, _start
+from .extra import LC_ADD, LC_AXPY, LC_SUB, _Chain, _Dev, _real, _run_chain, _start
 from .sparse import CsrOperator, _next_pow2
 from .triangular import MAX_COLS, TriangularOperator, canonical_triangle
 
@@ -124,10 +124,7 @@ def _stationary(update, A, b, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxit
     if callback is not None:
         callback(D.host(x), D.host(r))
 
-    def norm(v):
-        return np.sqrt(_real(D.dot(v, v)))
-
-    resnorms = [D.cols(norm(r))]
+    first = D.cols(np.sqrt(_real(D.dot(r, r))))
     C = _Chain(D, ["f", "nr"])
     if factor is not None:
         C.set("f", factor)
@@ -140,10 +137,8 @@ def _stationary(update, A, b, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxit
     elif kind == "ssor":
         tri = _TriUpdate(D, data[0])
         tri.scale = _diag_vector(D, data[1])
-    criterion = np.maximum(tol * resnorms[0], atol)
-    C.set(None, prob.pad_cols(criterion, np.inf))
 
-    def step(st):
+    def step(st, _k):
         if kind == "scale":
             C.lc(LC_AXPY, x, x, st, y=r, a="f")  # x += omega * r
         elif kind == "jacobi":
@@ -160,23 +155,5 @@ def _stationary(update, A, b, x0=None, inner=None, tol=1e-5, atol=1.0e-15, maxit
         C.norm(r, None, "nr", st)
         C.check("nr", st)
 
-    k = 0
-    success = False
-    while True:
-        if np.all(resnorms[-1] <= criterion):  # no explicit-residual re-check (stationary.py:138-140)
-            success = True
-            break
-        if k == maxiter:
-            break
-        steps = _chunks(D, callback) if maxiter is None else min(_chunks(D, callback), maxiter - k)
-        C.begin()
-        for st in range(steps):
-            step(st)
-        rows, _ = C.end(steps)
-        for row in rows:
-            if callback is not None:
-                callback(D.host(x), D.host(r))
-            resnorms.append(D.cols(row))
-            k += 1
-    xk = D.host_final(x)
-    return xk if success else None, Info(success, xk, k, resnorms, renumbered=prob.A.renumbered)
+    # no explicit-residual recheck (stationary.py:138-140)
+    return _run_chain(D, C, x, r, first, None, step, tol, atol, maxiter, callback)
