@@ -335,11 +335,38 @@ int kry_prog_trisolve(kry_prog *p, const kry_tri *T, const kry_vec *y, kry_vec *
  * null arrays to size them. A row without a diagonal entry is KRY_ESINGULAR,
  * an entry on the wrong side of the diagonal or an unsorted row KRY_EINVAL.
  * kry_tri_create: analysis + upload (a zero diagonal value: KRY_ESINGULAR).
- * kry_tri_info: info[0..5] = the five values above and the image's bytes. */
+ * kry_tri_info: info[0..5] = the five values above and the image's bytes.
+ * kry_tri_plan_ordered / kry_tri_create_ordered (kry_version() >= 109): the
+ * same over an elimination order, rank[i] = row i's position in it (a
+ * permutation of 0..n-1, else KRY_EINVAL). "Lower" then means rank[j] < rank[i]
+ * for every off-diagonal (i, j) and "upper" the reverse (an entry on the wrong
+ * side: KRY_EINVAL); the levels come from that dependency graph, the rows are
+ * ordered by (level, rank), and a row's terms are summed in ascending rank[j].
+ * The solve is bitwise the solve of the explicitly permuted triangle
+ * T[perm][:, perm] (rank[perm[r]] = r), but T, y and x stay in the caller's
+ * numbering and no permutation pass runs over the vectors. rank = NULL is the
+ * identity: exactly kry_tri_plan / kry_tri_create. */
 int kry_tri_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int lower, int64_t *info,
                  int32_t *level, int32_t *order, int32_t *launch, int32_t *widths);
 int kry_tri_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,
                    int dtype, int itype, int lower, kry_tri **out);
+int kry_tri_plan_ordered(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int lower,
+                         const int32_t *rank, int64_t *info, int32_t *level, int32_t *order, int32_t *launch,
+                         int32_t *widths);
+int kry_tri_create_ordered(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices,
+                           const void *data, int dtype, int itype, int lower, const int32_t *rank, kry_tri **out);
+/* Multicolour ordering (kry_version() >= 109; host-only, no device). In the
+ * caller's numbering a stencil's triangles have thousands of thin dependency
+ * levels, one launch each; eliminating colour by colour makes every level a
+ * whole colour. Graph: the stored pattern of A + A^T without the diagonal
+ * (explicit zeros are edges). Greedy first-fit in ascending row order:
+ * color[i] = the smallest integer >= 0 that no neighbour j < i has
+ * (deterministic, O(nnz)). perm[n] lists the rows by (colour, row): the
+ * permuted matrix is A[perm][:, perm], and rank[perm[r]] = r is the
+ * elimination order kry_tri_create_ordered takes. info[0] = colours, info[1] =
+ * rows of the largest colour. Null arrays size the call. */
+int kry_color_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int64_t *info,
+                   int32_t *color, int32_t *perm);
 int kry_tri_destroy(kry_tri *T);
 int kry_tri_info(const kry_tri *T, int64_t *info);
 int kry_tri_solve(kry_ctx *ctx, const kry_tri *T, const kry_vec *y, kry_vec *x);
@@ -373,6 +400,17 @@ int kry_tri_solve(kry_ctx *ctx, const kry_tri *T, const kry_vec *y, kry_vec *x);
  * kry_precond_create / add_tri / add_scale / destroy: the stage list. Stages
  * are borrowed: the caller keeps the kry_tri / kry_vec handles alive as long
  * as the preconditioner, which must match them in n and dtype.
+ * kry_precond_fuse (kry_version() >= 109; after the last stage, for objects
+ * whose solves were built under a multicolour elimination order): apply the
+ * stages in fewer launches, bitwise the stage-by-stage apply. A row scale in
+ * front of a solve goes into that solve (num = (y * s) - acc, the product
+ * rounded first); where the last level of a solve is a launch of its own and
+ * the first level of the next solve holds exactly the same rows without
+ * off-diagonal entries (two colours), one launch does both, t = (y - acc) / d1,
+ * u = t * s, z = u / d2 in that order. KRY_PRECOND_FUSE=0, read by
+ * kry_precond_create, makes this call a no-op.
+ * kry_precond_info: info[0..4] = launches per apply, fused (0/1), stages,
+ * scales folded into a solve, fused level boundaries.
  * kry_precond_apply: y = P x (k <= 64 columns, a power of two; y may alias x).
  * kry_prog_precond: the same as a chain step.
  * kry_*_set_precond: a factorised preconditioner in slot 0 = M, 1 = Ml, 2 = Mr
@@ -389,6 +427,8 @@ int kry_precond_create(kry_ctx *ctx, int64_t n, int dtype, kry_precond **out);
 int kry_precond_destroy(kry_precond *P);
 int kry_precond_add_tri(kry_precond *P, const kry_tri *T);
 int kry_precond_add_scale(kry_precond *P, const kry_vec *d);
+int kry_precond_fuse(kry_precond *P);
+int kry_precond_info(const kry_precond *P, int64_t *info);
 int kry_precond_apply(kry_ctx *ctx, const kry_precond *P, const kry_vec *x, kry_vec *y);
 int kry_prog_precond(kry_prog *p, const kry_precond *P, const kry_vec *x, kry_vec *y, int32_t step);
 int kry_cg_set_precond(kry_cg *s, int32_t slot, const kry_precond *P);

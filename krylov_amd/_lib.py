@@ -155,6 +155,9 @@ _SIGNATURES = {
     "kry_prog_trisolve": [_vp, _vp, _vp, _vp, _i32],
     "kry_tri_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _int, _ip64, _vp, _vp, _vp, _vp],
     "kry_tri_create": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _pvp],
+    "kry_tri_plan_ordered": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _int, _vp, _ip64, _vp, _vp, _vp, _vp],
+    "kry_tri_create_ordered": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _vp, _pvp],
+    "kry_color_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp, _vp],
     "kry_tri_destroy": [_vp],
     "kry_tri_info": [_vp, _ip64],
     "kry_tri_solve": [_vp, _vp, _vp, _vp],
@@ -164,6 +167,8 @@ _SIGNATURES = {
     "kry_precond_destroy": [_vp],
     "kry_precond_add_tri": [_vp, _vp],
     "kry_precond_add_scale": [_vp, _vp],
+    "kry_precond_fuse": [_vp],
+    "kry_precond_info": [_vp, _ip64],
     "kry_precond_apply": [_vp, _vp, _vp, _vp],
     "kry_prog_precond": [_vp, _vp, _vp, _vp, _i32],
     "kry_cg_set_precond": [_vp, _i32, _vp],
@@ -373,25 +378,52 @@ def rs_plan(indptr, indices):
             "colrank": colrank}
 
 
-def tri_plan(indptr, indices, lower=True):
+def tri_plan(indptr, indices, lower=True, rank=None):
     """Host-only analysis of a sparse triangular solve (kry_tri_plan):
     {"levels", "launches", "slices", "slots", "max_level", "level" (per row,
     from 1), "order" (rows by (level, row)), "launch" (level boundaries of the
-    launches), "widths" (per slice)}."""
+    launches), "widths" (per slice)}. ``rank``: an elimination order, rank[i]
+    = row i's position (kry_tri_plan_ordered; "order" is then by (level,
+    rank))."""
     indptr = np.ascontiguousarray(indptr)
     indices = np.ascontiguousarray(indices, dtype=indptr.dtype)
     n, nnz = indptr.shape[0] - 1, indices.shape[0]
     info = np.zeros(5, dtype=np.int64)
     ip64 = info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    args = (n, nnz, ptr(indptr), ptr(indices), itype_code(indptr.dtype), 1 if lower else 0, ip64)
-    check(lib.kry_tri_plan(*args, None, None, None, None))
+    head = (n, nnz, ptr(indptr), ptr(indices), itype_code(indptr.dtype), 1 if lower else 0)
+    if rank is None:
+        plan, args = lib.kry_tri_plan, head + (ip64,)
+    else:
+        rank = np.ascontiguousarray(rank, dtype=np.int32)
+        if rank.shape != (n,):
+            raise ValueError("rank must have one entry per row")
+        plan, args = lib.kry_tri_plan_ordered, head + (ptr(rank), ip64)
+    check(plan(*args, None, None, None, None))
     level = np.zeros(n, dtype=np.int32)
     order = np.zeros(n, dtype=np.int32)
     launch = np.zeros(int(info[1]) + 1, dtype=np.int32)
     widths = np.zeros(int(info[2]), dtype=np.int32)
-    check(lib.kry_tri_plan(*args, ptr(level), ptr(order), ptr(launch), ptr(widths)))
+    check(plan(*args, ptr(level), ptr(order), ptr(launch), ptr(widths)))
     return {"levels": int(info[0]), "launches": int(info[1]), "slices": int(info[2]), "slots": int(info[3]),
             "max_level": int(info[4]), "level": level, "order": order, "launch": launch, "widths": widths}
+
+
+def color_plan(indptr, indices):
+    """Host-only multicolour ordering of a square CSR pattern
+    (kry_color_plan): {"colors" (count), "max_color" (rows of the largest),
+    "color" (per row, greedy first-fit over A + A^T in row order), "perm" (rows
+    by (colour, row))}."""
+    indptr = np.ascontiguousarray(indptr)
+    indices = np.ascontiguousarray(indices, dtype=indptr.dtype)
+    n, nnz = indptr.shape[0] - 1, indices.shape[0]
+    info = np.zeros(2, dtype=np.int64)
+    ip64 = info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    args = (n, nnz, ptr(indptr), ptr(indices), itype_code(indptr.dtype), ip64)
+    check(lib.kry_color_plan(*args, None, None))
+    color = np.zeros(n, dtype=np.int32)
+    perm = np.zeros(n, dtype=np.int32)
+    check(lib.kry_color_plan(*args, ptr(color), ptr(perm)))
+    return {"colors": int(info[0]), "max_color": int(info[1]), "color": color, "perm": perm}
 
 
 def ilu0_plan(indptr, indices):

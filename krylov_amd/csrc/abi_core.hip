@@ -431,7 +431,7 @@ extern "C" {
 // kry_gmres_xk_device. 107: uniform slot columns of the diagonal-offset image
 // (kry_csr_info_n: two more values; kry_dia_uniform_plan; kry_csr_compare:
 // bits 23-25).
-int kry_version(void) { return 108; }
+int kry_version(void) { return 109; }
 
 #ifndef KRY_BUILD_ID
 #define KRY_BUILD_ID "unknown"

@@ -860,16 +860,29 @@ static void cb_plan_host(int64_t n, int64_t nnz, const I *ip, const I *ix, int64
 
 // ------------------------------------------- sparse triangular solve plan
 template <typename I>
-void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriPlan &p) {
+void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriPlan &p, const int32_t *rank) {
   check_csr(n, nnz, ip, ix);
   KRY_REQUIRE(n < INT32_MAX - kSlice, KRY_EUNSUPPORTED, "the triangular image numbers rows in int32");
   p = TriPlan();
   p.n = n;
   p.level.assign((size_t)n, 0);
+  // the elimination order: at[q] = the row at position q (the identity without a rank)
+  std::vector<int32_t> at;
+  if (rank) {
+    at.assign((size_t)n, -1);
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t r = rank[i];
+      KRY_REQUIRE(r >= 0 && r < n && at[(size_t)r] < 0, KRY_EINVAL, "rank must be a permutation of 0..n-1");
+      at[(size_t)r] = (int32_t)i;
+    }
+    p.rank.assign(rank, rank + n);
+  }
+  auto pos = [&](int64_t i) { return rank ? (int64_t)rank[i] : i; };
+  auto row_at = [&](int64_t q) { return rank ? (int64_t)at[(size_t)q] : q; };
   // levels: a lower triangle's rows depend on earlier rows, an upper one's on later rows
   int32_t nlev = 0;
   for (int64_t q = 0; q < n; ++q) {
-    const int64_t i = lower ? q : n - 1 - q;
+    const int64_t i = row_at(lower ? q : n - 1 - q);
     int32_t lev = 1;
     bool diag = false;
     for (int64_t e = (int64_t)ip[i]; e < (int64_t)ip[i + 1]; ++e) {
@@ -880,7 +893,7 @@ void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriP
         diag = true;
         continue;
       }
-      KRY_REQUIRE(lower ? j < i : j > i, KRY_EINVAL, "an entry on the wrong side of the diagonal");
+      KRY_REQUIRE(lower ? pos(j) < pos(i) : pos(j) > pos(i), KRY_EINVAL, "an entry on the wrong side of the diagonal");
       lev = std::max(lev, p.level[(size_t)j] + 1);
     }
     KRY_REQUIRE(diag, KRY_ESINGULAR, "singular matrix: no diagonal entry in row " + std::to_string(i));
@@ -888,14 +901,17 @@ void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriP
     nlev = std::max(nlev, lev);
   }
   p.nlevels = nlev;
-  // rows by (level, row): a counting sort
+  // rows by (level, position in the elimination order): a counting sort
   p.lrow.assign((size_t)nlev + 1, 0);
   for (int64_t i = 0; i < n; ++i) ++p.lrow[(size_t)p.level[(size_t)i]];
   for (int32_t l = 0; l < nlev; ++l) p.lrow[(size_t)l + 1] += p.lrow[(size_t)l];
   p.order.assign((size_t)n, 0);
   {
-    std::vector<int32_t> at(p.lrow.begin(), p.lrow.end() - (nlev ? 1 : 0));
-    for (int64_t i = 0; i < n; ++i) p.order[(size_t)at[(size_t)p.level[(size_t)i] - 1]++] = (int32_t)i;
+    std::vector<int32_t> next(p.lrow.begin(), p.lrow.end() - (nlev ? 1 : 0));
+    for (int64_t q = 0; q < n; ++q) {
+      const int64_t i = row_at(q);
+      p.order[(size_t)next[(size_t)p.level[(size_t)i] - 1]++] = (int32_t)i;
+    }
   }
   // slices of up to kSlice rows inside a level
   p.lslice.assign((size_t)nlev + 1, 0);
@@ -942,6 +958,8 @@ void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int3
   par_fill(diag, (size_t)p.nslices * kSlice + 1, V(1));
   par_fill(col, (size_t)p.nslots + 1, (int32_t)-1);
   par_fill(val, (size_t)p.nslots + 1, V(0));
+  const int32_t *rank = p.rank.empty() ? nullptr : p.rank.data();
+  std::vector<int64_t> ent;  // a row's off-diagonal entries in ascending rank
   for (int64_t l = 0; l < p.nlevels; ++l)
     for (int64_t s = p.lslice[(size_t)l]; s < p.lslice[(size_t)l + 1]; ++s) {
       const int64_t a = p.lrow[(size_t)l] + (int64_t)kSlice * (s - p.lslice[(size_t)l]);
@@ -950,16 +968,30 @@ void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int3
         const int64_t i = p.order[(size_t)q], r = q - a;
         rows[(size_t)(s * kSlice + r)] = (int32_t)i;
         int64_t j = 0;
+        ent.clear();
         for (int64_t e = (int64_t)ip[i]; e < (int64_t)ip[i + 1]; ++e) {
           if ((int64_t)ix[e] == i) {
             KRY_REQUIRE(dv[e] != V(0), KRY_ESINGULAR, "singular matrix: zero diagonal in row " + std::to_string(i));
             diag[(size_t)(s * kSlice + r)] = dv[e];
             continue;
           }
+          if (rank) {
+            ent.push_back(e);
+            continue;
+          }
           const size_t slot = (size_t)(p.sptr[(size_t)s] + j * kSlice + r);
           col[slot] = (int32_t)ix[e];
           val[slot] = dv[e];
           ++j;
+        }
+        if (rank) {
+          std::sort(ent.begin(), ent.end(), [&](int64_t a, int64_t b) { return rank[ix[a]] < rank[ix[b]]; });
+          for (const int64_t e : ent) {
+            const size_t slot = (size_t)(p.sptr[(size_t)s] + j * kSlice + r);
+            col[slot] = (int32_t)ix[e];
+            val[slot] = dv[e];
+            ++j;
+          }
         }
       }
     }
@@ -988,12 +1020,60 @@ void ilu0_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, Ilu0Plan &p) {
   tri_plan(n, (int64_t)lx.size(), lp.data(), lx.data(), true, p.tri);
 }
 
+// --------------------------------------------------- multicolour ordering
+template <typename I>
+void color_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, std::vector<int32_t> &color,
+                std::vector<int32_t> &perm, int64_t *ncolors, int64_t *max_rows) {
+  check_csr(n, nnz, ip, ix);
+  KRY_REQUIRE(n < INT32_MAX, KRY_EUNSUPPORTED, "the colouring numbers rows in int32");
+  // the transposed half of the graph: tx[tp[c] .. tp[c + 1]) = the rows j < c that store (j, c)
+  std::vector<int64_t> tp((size_t)n + 1, 0);
+  for (int64_t j = 0; j < n; ++j)
+    for (int64_t e = (int64_t)ip[j]; e < (int64_t)ip[j + 1]; ++e)
+      if ((int64_t)ix[e] > j) ++tp[(size_t)ix[e] + 1];
+  for (int64_t c = 0; c < n; ++c) tp[(size_t)c + 1] += tp[(size_t)c];
+  std::vector<int32_t> tx((size_t)tp[(size_t)n]);
+  {
+    std::vector<int64_t> next(tp.begin(), tp.end() - 1);
+    for (int64_t j = 0; j < n; ++j)
+      for (int64_t e = (int64_t)ip[j]; e < (int64_t)ip[j + 1]; ++e)
+        if ((int64_t)ix[e] > j) tx[(size_t)next[(size_t)ix[e]]++] = (int32_t)j;
+  }
+  color.assign((size_t)n, 0);
+  std::vector<int64_t> seen;  // seen[c] = the last row with a neighbour of colour c, plus 1
+  std::vector<int32_t> count;
+  for (int64_t i = 0; i < n; ++i) {
+    for (int64_t e = (int64_t)ip[i]; e < (int64_t)ip[i + 1]; ++e)
+      if ((int64_t)ix[e] < i) seen[(size_t)color[(size_t)ix[e]]] = i + 1;
+    for (int64_t e = tp[(size_t)i]; e < tp[(size_t)i + 1]; ++e) seen[(size_t)color[(size_t)tx[(size_t)e]]] = i + 1;
+    size_t c = 0;
+    while (c < seen.size() && seen[c] == i + 1) ++c;
+    if (c == seen.size()) {
+      seen.push_back(0);
+      count.push_back(0);
+    }
+    color[(size_t)i] = (int32_t)c;
+    ++count[c];
+  }
+  *ncolors = (int64_t)count.size();
+  *max_rows = 0;
+  std::vector<int64_t> next(count.size() + 1, 0);
+  for (size_t c = 0; c < count.size(); ++c) {
+    *max_rows = std::max<int64_t>(*max_rows, count[c]);
+    next[c + 1] = next[c] + count[c];
+  }
+  perm.assign((size_t)n, 0);
+  for (int64_t i = 0; i < n; ++i) perm[(size_t)next[(size_t)color[(size_t)i]]++] = (int32_t)i;
+}
+
 // explicit instantiations: the combinations kry_csr_create dispatches
 #define KRY_HOST_I(I)                                                                                             \
   template void check_csr<I>(int64_t, int64_t, const I *, const I *);                                            \
   template bool scattered<I>(int64_t, const I *, const I *);                                                     \
   template bool rcm_order<I>(int64_t, const I *, const I *, int64_t, std::vector<int32_t> &, int64_t *);          \
-  template void tri_plan<I>(int64_t, int64_t, const I *, const I *, bool, TriPlan &);                            \
+  template void tri_plan<I>(int64_t, int64_t, const I *, const I *, bool, TriPlan &, const int32_t *);           \
+  template void color_plan<I>(int64_t, int64_t, const I *, const I *, std::vector<int32_t> &,                   \
+                              std::vector<int32_t> &, int64_t *, int64_t *);                                     \
   template void ilu0_plan<I>(int64_t, int64_t, const I *, const I *, Ilu0Plan &);                               \
   template void sell_plan<I>(int64_t, const I *, std::vector<int64_t> *, std::vector<int32_t> *, int64_t *,     \
                              int64_t *, int64_t *);                                                              \
@@ -1167,15 +1247,16 @@ int kry_rs_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices,
   KRY_API_END
 }
 
-int kry_tri_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int lower, int64_t *info,
-                 int32_t *level, int32_t *order, int32_t *launch, int32_t *widths) {
+int kry_tri_plan_ordered(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int lower,
+                         const int32_t *rank, int64_t *info, int32_t *level, int32_t *order, int32_t *launch,
+                         int32_t *widths) {
   KRY_API_BEGIN
   KRY_REQUIRE(indptr && info && n >= 0 && nnz >= 0 && (nnz == 0 || indices), KRY_EINVAL, "bad plan arguments");
   TriPlan p;
   if (itype == KRY_I32)
-    tri_plan(n, nnz, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices), lower != 0, p);
+    tri_plan(n, nnz, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices), lower != 0, p, rank);
   else if (itype == KRY_I64)
-    tri_plan(n, nnz, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices), lower != 0, p);
+    tri_plan(n, nnz, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices), lower != 0, p, rank);
   else
     throw Error{KRY_EINVAL, "bad itype"};
   info[0] = p.nlevels;
@@ -1187,6 +1268,29 @@ int kry_tri_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices
   if (order) std::copy(p.order.begin(), p.order.end(), order);
   if (launch) std::copy(p.launch.begin(), p.launch.end(), launch);
   if (widths) std::copy(p.swidth.begin(), p.swidth.end(), widths);
+  KRY_API_END
+}
+
+int kry_tri_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int lower, int64_t *info,
+                 int32_t *level, int32_t *order, int32_t *launch, int32_t *widths) {
+  return kry_tri_plan_ordered(n, nnz, indptr, indices, itype, lower, nullptr, info, level, order, launch, widths);
+}
+
+int kry_color_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int64_t *info,
+                   int32_t *color, int32_t *perm) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(indptr && info && n >= 0 && nnz >= 0 && (nnz == 0 || indices), KRY_EINVAL, "bad plan arguments");
+  std::vector<int32_t> c, p;
+  if (itype == KRY_I32)
+    color_plan(n, nnz, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices), c, p, &info[0],
+               &info[1]);
+  else if (itype == KRY_I64)
+    color_plan(n, nnz, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices), c, p, &info[0],
+               &info[1]);
+  else
+    throw Error{KRY_EINVAL, "bad itype"};
+  if (color) std::copy(c.begin(), c.end(), color);
+  if (perm) std::copy(p.begin(), p.end(), perm);
   KRY_API_END
 }
 

@@ -177,6 +177,12 @@ bool rs_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_sl
 // kTriGroupRows rows in total is one launch of one workgroup (a workgroup
 // barrier between its levels); a level above kTriGroupRows rows is a launch
 // of its own over many workgroups. No launch waits on another workgroup.
+// With an elimination order (`rank`, a permutation: rank[i] = row i's position)
+// "lower" means rank[j] < rank[i] for every off-diagonal (i, j) and "upper" the
+// reverse, `order` lists the rows by (level, rank), and tri_fill stores a row's
+// off-diagonal entries in ascending rank[j]: the plan and image of the
+// explicitly permuted triangle, in the caller's numbering. rank == null is the
+// identity.
 struct TriPlan {
   int64_t n = 0, nlevels = 0, nslices = 0, nslots = 0, max_level_rows = 0;
   std::vector<int32_t> level;   // n, from 1
@@ -186,12 +192,15 @@ struct TriPlan {
   std::vector<int32_t> swidth;  // nslices
   std::vector<int64_t> sptr;    // nslices + 1, slots
   std::vector<int32_t> launch;  // launches + 1, level boundaries
+  std::vector<int32_t> rank;    // n, the elimination order (empty: the identity)
 };
 template <typename I>
-void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriPlan &p);
+void tri_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, bool lower, TriPlan &p,
+              const int32_t *rank = nullptr);
 // The image of the plan: rows[64 nslices] (-1 = padding), diag[64 nslices]
 // (1 on padding), col / val[nslots] (col -1, val 0 = padding), every row's
-// off-diagonal entries in stored order. A zero diagonal is KRY_ESINGULAR.
+// off-diagonal entries in stored order (in ascending rank under an elimination
+// order). A zero diagonal is KRY_ESINGULAR.
 template <typename I, typename V>
 void tri_fill(const TriPlan &p, const I *ip, const I *ix, const V *dv, hvec<int32_t> &rows, hvec<V> &diag,
               hvec<int32_t> &col, hvec<V> &val);
@@ -209,5 +218,13 @@ struct Ilu0Plan {
 };
 template <typename I>
 void ilu0_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, Ilu0Plan &p);
+
+// Multicolour ordering (kry_color_plan): greedy first-fit colouring, rows
+// ascending, of the graph of the stored pattern of A + A^T without the
+// diagonal (explicit zeros are edges): color[i] = the smallest integer >= 0
+// that no neighbour j < i has. perm lists the rows by (colour, row). O(nnz).
+template <typename I>
+void color_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, std::vector<int32_t> &color,
+                std::vector<int32_t> &perm, int64_t *ncolors, int64_t *max_rows);
 
 }  // namespace kry

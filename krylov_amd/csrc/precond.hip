@@ -20,7 +20,14 @@
 // between its levels; a larger level is a launch of its own over many
 // workgroups. No kernel waits on another workgroup: stream order is the only
 // cross-workgroup dependency.
+//
+// A multicolour kry_precond (kry_precond_fuse) applies its stages in fewer
+// launches, bitwise the stage-by-stage apply: a row scale goes into the solve
+// behind it, and where one solve's last level and the next solve's first are
+// the same rows (two colours) they are one launch (tri.hip). KRY_PRECOND_FUSE=0
+// turns both off.
 #include <climits>
+#include <cstdlib>
 #include <string>
 
 #include "host_image.hpp"
@@ -201,10 +208,71 @@ void vec_check(const kry_precond *P, const kry_vec *x, const kry_vec *y) {
 
 namespace kry {
 
+// The fused form of the stage list: every scale directly in front of a solve
+// is folded into it, and a solve hands its last level to a boundary launch
+// when the next solve (behind at most one scale) matches it, it takes no
+// folded scale itself and keeps a level of its own.
+static void fuse_plan(kry_precond *P) {
+  const size_t ns = P->stages.size();
+  P->fuse.assign(ns, kry_precond::Fuse());
+  for (size_t i = 0; i < ns; ++i) {
+    const kry_precond::Stage &s = P->stages[i];
+    if (!s.tri) {
+      if (i + 1 < ns && P->stages[i + 1].tri) {
+        P->fuse[i].folded = true;
+        P->fuse[i + 1].pre = s.scale;
+      }
+      continue;
+    }
+    const size_t j = (i + 1 < ns && !P->stages[i + 1].tri) ? i + 2 : i + 1;
+    if (j >= ns || !P->stages[j].tri || P->fuse[i].pre) continue;
+    if (!tri_boundary_match(s.tri, P->stages[j].tri)) continue;
+    if (P->fuse[i].skip_first && tri_launches(s.tri, true, false) == 0) continue;  // its only level is taken
+    P->fuse[i].boundary = true;
+    P->fuse[i].next = P->stages[j].tri;
+    P->fuse[i].mid = j == i + 2 ? P->stages[i + 1].scale : nullptr;
+    P->fuse[j].skip_first = true;
+  }
+}
+
+static int precond_launches(const kry_precond *P) {
+  int count = 0;
+  for (size_t i = 0; i < P->stages.size(); ++i) {
+    const kry_precond::Stage &s = P->stages[i];
+    if (P->fuse.empty()) {
+      count += s.tri ? tri_launches(s.tri, false, false) : 1;
+      continue;
+    }
+    const kry_precond::Fuse &f = P->fuse[i];
+    if (s.tri) count += tri_launches(s.tri, f.skip_first, f.boundary) + (f.boundary ? 1 : 0);
+    else if (!f.folded) ++count;
+  }
+  return count;
+}
+
 void precond_stages(const kry_precond *P, int k, const void *src, void *dst, const Ctrl *ctrl, int step,
                     hipStream_t st) {
   KRY_REQUIRE(!P->stages.empty(), KRY_EINVAL, "a preconditioner without stages");
   const void *in = src;
+  if (!P->fuse.empty()) {
+    KRY_REQUIRE(P->fuse.size() == P->stages.size(), KRY_EINVAL, "a stage was added after kry_precond_fuse");
+    for (size_t i = 0; i < P->stages.size(); ++i) {
+      const kry_precond::Stage &s = P->stages[i];
+      const kry_precond::Fuse &f = P->fuse[i];
+      if (s.tri) {
+        tri_solve_part(s.tri, k, in, dst, f.pre, f.skip_first, f.boundary, ctrl, step, st);
+        if (f.boundary) tri_boundary(s.tri, f.next, k, in, dst, f.mid, ctrl, step, st);
+      } else if (f.folded) {
+        continue;  // `in` stays: the next solve reads it times this scale
+      } else if (P->dtype == KRY_F64) {
+        scale_launch<double>(P->n, k, in, dst, s.scale, ctrl, step, st);
+      } else {
+        scale_launch<float>(P->n, k, in, dst, s.scale, ctrl, step, st);
+      }
+      in = dst;
+    }
+    return;
+  }
   for (const kry_precond::Stage &s : P->stages) {
     if (s.tri) tri_solve_raw(s.tri, k, in, dst, ctrl, step, st);
     else if (P->dtype == KRY_F64) scale_launch<double>(P->n, k, in, dst, s.scale, ctrl, step, st);
@@ -261,7 +329,34 @@ int kry_precond_create(kry_ctx *ctx, int64_t n, int dtype, kry_precond **out) {
   P->ctx = ctx;
   P->n = n;
   P->dtype = dtype;
+  const char *fuse = getenv("KRY_PRECOND_FUSE");
+  P->fuse_allowed = !(fuse && fuse[0] == '0' && fuse[1] == 0);
   *out = P;
+  KRY_API_END
+}
+
+int kry_precond_fuse(kry_precond *P) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(P, KRY_EINVAL, "null argument");
+  KRY_REQUIRE(!P->stages.empty(), KRY_EINVAL, "a preconditioner without stages");
+  P->fused = P->fuse_allowed;
+  if (P->fused) fuse_plan(P);
+  KRY_API_END
+}
+
+int kry_precond_info(const kry_precond *P, int64_t *info) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(P && info, KRY_EINVAL, "null argument");
+  info[0] = precond_launches(P);
+  info[1] = P->fused ? 1 : 0;
+  info[2] = (int64_t)P->stages.size();
+  int64_t folded = 0, boundaries = 0;
+  for (const kry_precond::Fuse &f : P->fuse) {
+    folded += f.folded ? 1 : 0;
+    boundaries += f.boundary ? 1 : 0;
+  }
+  info[3] = folded;
+  info[4] = boundaries;
   KRY_API_END
 }
 

@@ -22,6 +22,20 @@ struct kry_precond {
   int64_t n = 0;
   int dtype = 0;
   std::vector<Stage> stages;
+  // The fused apply of a multicolour object (kry_precond_fuse; precond.hip
+  // fuse_plan), one entry per stage. A scale stage with `folded` set launches
+  // nothing: the next solve multiplies its right-hand side by it (`pre`). A
+  // solve with `boundary` leaves its last level to one launch that also does
+  // the first level of the solve `next` (and the scale `mid` between them),
+  // which then starts at its second level (`skip_first`).
+  struct Fuse {
+    bool folded = false, skip_first = false, boundary = false;
+    const void *pre = nullptr, *mid = nullptr;
+    const kry_tri *next = nullptr;
+  };
+  bool fuse_allowed = true;  // KRY_PRECOND_FUSE, read at creation
+  bool fused = false;
+  std::vector<Fuse> fuse;    // empty: every stage is its own launches
 };
 
 namespace kry {
@@ -29,6 +43,19 @@ namespace kry {
 // tri.hip: kry_tri_solve on raw n x k blocks (k a power of two <= 64; x may alias y)
 void tri_solve_raw(const kry_tri *T, int k, const void *y, void *x, const Ctrl *ctrl, int step, hipStream_t st);
 void tri_shape(const kry_tri *T, int64_t *n, int *dtype);
+// tri.hip, for a fused kry_precond. tri_solve_part: the solve without its
+// first and / or last level, its right-hand side times the row scale `scale`
+// when non-null. tri_boundary_match: T's last level is a launch of its own and
+// holds exactly the rows of next's first level, which has no off-diagonal
+// entry (both built under an elimination order). tri_boundary: that level of
+// both solves, with the row scale between them when non-null, in one launch.
+// tri_launches: the launches of tri_solve_part.
+void tri_solve_part(const kry_tri *T, int k, const void *y, void *x, const void *scale, bool skip_first,
+                    bool skip_last, const Ctrl *ctrl, int step, hipStream_t st);
+bool tri_boundary_match(const kry_tri *T, const kry_tri *next);
+void tri_boundary(const kry_tri *T, const kry_tri *next, int k, const void *y, void *x, const void *scale,
+                  const Ctrl *ctrl, int step, hipStream_t st);
+int tri_launches(const kry_tri *T, bool skip_first, bool skip_last);
 // precond.hip: dst = P src, stage by stage (the first stage reads src, the
 // others work in place on dst; dst may alias src)
 void precond_stages(const kry_precond *P, int k, const void *src, void *dst, const Ctrl *ctrl, int step,

@@ -8,6 +8,12 @@ shows the analysis without a device); a solve is a fixed sequence of launches
 ordered by the stream alone, and every row is summed in its stored order, so
 the result is bitwise repeatable and independent of the launch plan and of the
 number of right-hand sides.
+
+``order=perm`` solves over an elimination order instead of the row numbers
+(``kry_tri_create_ordered``): T is triangular in the order perm lists the rows
+in, the levels follow that order, and the solve is bitwise the solve of the
+explicitly permuted ``T[perm][:, perm]``, while T and the vectors stay in the
+caller's numbering.
 """
 import ctypes
 
@@ -22,10 +28,24 @@ from .sparse import _next_pow2
 MAX_COLS = 64  # the chain's limit (kry_prog)
 
 
-def canonical_triangle(T, lower=True):
+def rank_of(order, n):
+    """rank[i] = the position of row i in the elimination order ``order`` (a
+    permutation of 0..n-1), int32."""
+    perm = np.asarray(order)
+    if perm.shape != (n,) or not np.issubdtype(perm.dtype, np.integer):
+        raise ValueError(f"order must be a permutation of 0..{n - 1} as an integer array of shape ({n},)")
+    if n and not np.array_equal(np.sort(perm), np.arange(n)):
+        raise ValueError(f"order must be a permutation of 0..{n - 1}")
+    rank = np.empty(n, dtype=np.int32)
+    rank[perm] = np.arange(n, dtype=np.int32)
+    return rank
+
+
+def canonical_triangle(T, lower=True, rank=None):
     """T as a canonical CSR (sorted rows, duplicates summed) after the checks
-    that need no device: square, real, triangular on the stated side, a full
-    non-zero diagonal (``numpy.linalg.LinAlgError`` otherwise, as scipy)."""
+    that need no device: square, real, triangular on the stated side (in the
+    elimination order ``rank`` when given), a full non-zero diagonal
+    (``numpy.linalg.LinAlgError`` otherwise, as scipy)."""
     if scipy.sparse.issparse(T):
         csr = scipy.sparse.csr_matrix(T, copy=True)
     elif isinstance(T, np.ndarray) and T.ndim == 2:
@@ -38,12 +58,23 @@ def canonical_triangle(T, lower=True):
         raise TypeError("complex matrices are outside the MI355X path (float32/float64 only)")
     csr.sum_duplicates()
     csr.sort_indices()
-    other = scipy.sparse.triu(csr, 1) if lower else scipy.sparse.tril(csr, -1)
-    if other.count_nonzero():
-        raise ValueError(f"T is not {'lower' if lower else 'upper'} triangular")
-    if other.nnz:  # stored zeros on the other side
-        csr = (scipy.sparse.tril(csr) if lower else scipy.sparse.triu(csr)).tocsr()
-        csr.sort_indices()
+    if rank is not None:
+        if rank.shape[0] != csr.shape[0]:
+            raise ValueError("order must have one entry per row")
+        rows = np.repeat(np.arange(csr.shape[0]), np.diff(csr.indptr))
+        wrong = rank[csr.indices] > rank[rows] if lower else rank[csr.indices] < rank[rows]
+        if np.any(csr.data[wrong] != 0):
+            raise ValueError(f"T is not {'lower' if lower else 'upper'} triangular in the given order")
+        if np.any(wrong):  # stored zeros on the other side
+            csr = scipy.sparse.csr_matrix((csr.data[~wrong], (rows[~wrong], csr.indices[~wrong])), shape=csr.shape)
+            csr.sort_indices()
+    else:
+        other = scipy.sparse.triu(csr, 1) if lower else scipy.sparse.tril(csr, -1)
+        if other.count_nonzero():
+            raise ValueError(f"T is not {'lower' if lower else 'upper'} triangular")
+        if other.nnz:  # stored zeros on the other side
+            csr = (scipy.sparse.tril(csr) if lower else scipy.sparse.triu(csr)).tocsr()
+            csr.sort_indices()
     d = csr.diagonal()  # 0 for a stored zero and for a missing entry alike
     if csr.shape[0] and np.any(d == 0):
         raise np.linalg.LinAlgError(f"T is singular: zero entry on diagonal (row {int(np.argmax(d == 0))})")
@@ -54,10 +85,16 @@ class TriangularOperator:
     """A sparse triangular matrix on the device. ``T``: scipy.sparse matrix
     or dense array, triangular on the side ``lower`` says, in the caller's
     numbering. ``dtype``: the dtype of the vectors it will solve for (its
-    values are stored in it; default T's own, float32 or float64)."""
+    values are stored in it; default T's own, float32 or float64). ``order``:
+    an elimination order (a permutation listing the rows first to last, e.g.
+    ``multicolor_ordering(A)[1]``) in which T is triangular; default the row
+    numbers."""
 
-    def __init__(self, T, lower=True, device=None, ctx=None, dtype=None):
-        csr = canonical_triangle(T, lower)
+    def __init__(self, T, lower=True, device=None, ctx=None, dtype=None, order=None):
+        n = T.shape[0] if hasattr(T, "shape") and len(T.shape) == 2 else 0
+        rank = None if order is None else rank_of(order, n)
+        self.order = None if order is None else np.array(order, dtype=np.int32)
+        csr = canonical_triangle(T, lower, rank)
         dt = np.dtype(csr.dtype if dtype is None else dtype)
         if dt not in (np.float32, np.float64):
             dt = np.dtype(np.float64)
@@ -72,8 +109,12 @@ class TriangularOperator:
         indices = np.ascontiguousarray(csr.indices, dtype=itype)
         data = np.ascontiguousarray(csr.data, dtype=dt)
         h = ctypes.c_void_p()
-        check(lib.kry_tri_create(self.ctx.handle, self.n, self.nnz, _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data),
-                                 _lib.dtype_code(dt), _lib.itype_code(itype), 1 if lower else 0, ctypes.byref(h)))
+        head = (self.ctx.handle, self.n, self.nnz, _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data),
+                _lib.dtype_code(dt), _lib.itype_code(itype), 1 if lower else 0)
+        if rank is None:
+            check(lib.kry_tri_create(*head, ctypes.byref(h)))
+        else:
+            check(lib.kry_tri_create_ordered(*head, _lib.ptr(rank), ctypes.byref(h)))
         self.handle = h
         self._fin = _lib.own(self, lib.kry_tri_destroy, h)
 

@@ -5,14 +5,19 @@ Ilu0Preconditioner) as one JSON line.
     python tools/bench_precond.py [--out FILE] [--small]
 
 Workloads: poisson2d(1000) (SPD, 1,999 thin levels) and
-random_nonsym(2_000_000) (nonsymmetric, fat levels), b = ones. Per workload
-and preconditioner:
+random_nonsym(2_000_000) (nonsymmetric, fat levels), b = ones. Every
+preconditioner runs in natural order (ssor, ilu0) and in the multicolour order
+(ssor_mc, ilu0_mc: ordering="multicolor") in the same run. Per workload and
+preconditioner:
   setup_s        the constructor, whole (host analysis, uploads, images)
   factor_s       ILU(0) only: kry_ilu0_factor (analysis, upload, the
                  factorisation kernels, the values' way back)
   ms_per_apply   one P r on a device vector (k = 1): HIP events around a
-                 region of back-to-back applies, median of REGIONS regions
+                 region of back-to-back applies (5, or as many as fill 20 ms),
+                 median of REGIONS regions
   stages         levels / launches of every stage
+  launches, fused, colors   kernel launches per apply, whether the apply is the
+                 fused one, the number of colours (null in natural order)
 and per solver (cg on the SPD workload, gmres(30) = gmres_restarted on both)
 without a preconditioner and with each one (cg: M; gmres: Mr):
   steps, success, wall_s   iterations and host wall time of one whole call to
@@ -50,7 +55,9 @@ def time_apply(P):
     for _ in range(2):
         P.matvec_device(y, x)
     P.ctx.synchronize()
-    reps = 5
+    P.ctx.timer_start()
+    P.matvec_device(y, x)
+    reps = int(min(2000, max(5, np.ceil(20.0 / max(P.ctx.timer_stop(), 1e-3)))))
     ms = []
     for _ in range(REGIONS):
         P.ctx.timer_start()
@@ -71,6 +78,7 @@ def build(name, make):
     if "factor" in lay:
         out["factor_plan"] = lay["factor"]
     out["stages"] = [{k: s[k] for k in ("levels", "launches") if k in s} or s for s in lay["stages"]]
+    out["launches"], out["fused"], out["colors"] = lay["launches"], lay["fused"], lay["colors"]
     print(f"  {name}: setup {out['setup_s']:.2f} s, apply {out['ms_per_apply']:.3f} ms", file=sys.stderr, flush=True)
     return P, out
 
@@ -105,7 +113,9 @@ def workload(name, A, spd):
     out = {"n": n, "nnz": int(A.nnz), "precond": {}, "solves": {}}
     precs = {"none": None}
     for pname, make in (("ssor", lambda: krylov_amd.SsorPreconditioner(A, omega=1.0)),
-                        ("ilu0", lambda: krylov_amd.Ilu0Preconditioner(A))):
+                        ("ilu0", lambda: krylov_amd.Ilu0Preconditioner(A)),
+                        ("ssor_mc", lambda: krylov_amd.SsorPreconditioner(A, omega=1.0, ordering="multicolor")),
+                        ("ilu0_mc", lambda: krylov_amd.Ilu0Preconditioner(A, ordering="multicolor"))):
         try:
             precs[pname], out["precond"][pname] = build(pname, make)
         except Exception as e:  # recorded, not hidden: e.g. a singular pivot
