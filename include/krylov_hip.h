@@ -106,6 +106,14 @@ int kry_csr_destroy(kry_csr *A);
  * minres.py:95-151 for a renumbered A. */
 int kry_csr_create_like(kry_ctx *ctx, const kry_csr *like, int64_t n, int64_t nnz, const void *indptr,
                         const void *indices, const void *data, int dtype, int itype, kry_csr **out);
+/* kry_csr_create with the renumbering under the caller's control
+ * (kry_version() >= 110): renumber = 0 keeps the caller's numbering whatever
+ * the matrix looks like (KRY_RENUMBER is not consulted), anything else is
+ * kry_csr_create. The matrices of a factorised preconditioner's
+ * approximate-inverse stages (kry_precond_add_isai) are built this way: the
+ * stages work in the caller's numbering. */
+int kry_csr_create_ex(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices,
+                      const void *data, int dtype, int itype, int renumber, kry_csr **out);
 /* Renumbering (kry_version() >= 104). kry_csr_create renumbers a matrix whose
  * columns are scattered (the column-blocked test below) but whose graph has
  * narrow BFS levels (a mesh or stencil stored in a bad order) by reverse
@@ -409,8 +417,9 @@ int kry_tri_solve(kry_ctx *ctx, const kry_tri *T, const kry_vec *y, kry_vec *x);
  * off-diagonal entries (two colours), one launch does both, t = (y - acc) / d1,
  * u = t * s, z = u / d2 in that order. KRY_PRECOND_FUSE=0, read by
  * kry_precond_create, makes this call a no-op.
- * kry_precond_info: info[0..4] = launches per apply, fused (0/1), stages,
- * scales folded into a solve, fused level boundaries.
+ * kry_precond_info: info[0..4] = launches per apply (an approximate-inverse
+ * stage counts its SpMVs, 1 + 2 sweeps), fused (0/1), stages, scales folded
+ * into a solve, fused level boundaries.
  * kry_precond_apply: y = P x (k <= 64 columns, a power of two; y may alias x).
  * kry_prog_precond: the same as a chain step.
  * kry_*_set_precond: a factorised preconditioner in slot 0 = M, 1 = Ml, 2 = Mr
@@ -418,9 +427,44 @@ int kry_tri_solve(kry_ctx *ctx, const kry_tri *T, const kry_vec *y, kry_vec *x);
  * slot) and before start. The preconditioner's dtype must be the vectors'; an
  * operator renumbered at upload and a sharded solve are KRY_EUNSUPPORTED. The
  * inner products a matrix preconditioner's SpMV fuses (cg.py:205-209,
- * arnoldi.py:184-185) are taken by one element-wise pass after the stages. */
+ * arnoldi.py:184-185) are taken by one element-wise pass after the stages.
+ * Approximate-inverse solves (kry_version() >= 110; the incomplete sparse
+ * approximate inverse of Anzt, Huckle, Braeckle and Dongarra). A triangular
+ * factor T is replaced by a sparse W on T's own pattern with (W T) = I on that
+ * pattern, so a solve is one SpMV; relaxation sweeps x = x + W (y - T x) win
+ * back the exact solve's quality.
+ * kry_isai_lower: W's values (nnz values of `dtype`, in `values`) for a lower
+ * triangular CSR T with int32 indices, strictly sorted rows that each end in
+ * their diagonal entry. Row i with pattern J[0..m-1], J[m-1] = i:
+ *   w[m-1] = 1 / t(i,i)
+ *   for p = m-2 .. 0:
+ *     s = 0
+ *     for q = p+1 .. m-1 ascending, t(J[q],J[p]) stored: s = s - (t(J[q],J[p]) * w[q])
+ *     w[p] = s / t(J[p],J[p])
+ * with true divisions and the product rounded before the subtraction (no
+ * FMA): bitwise that sequential loop. The rows are independent: one launch,
+ * several short rows to a wavefront, the lookups of t(J[q],J[p]) binary
+ * searches run in parallel over q. info[0] = the smallest row whose diagonal is
+ * 0 or non-finite (-1: none; such a diagonal is KRY_ESINGULAR), info[1] = the
+ * longest row, info[2] = the kernel's time in microseconds. A row of more than
+ * 1024 entries is KRY_EUNSUPPORTED, a row that does not end in its diagonal or
+ * is not strictly sorted KRY_EINVAL. An upper factor U takes the same call on
+ * U^T, W_U = W(U^T)^T (the right inverse, (U W_U) = I on U's pattern), so
+ * W_U = W_L^T bitwise when U = L^T.
+ * kry_precond_add_isai: a stage x = W y, then `sweeps` times
+ * x = x + W (y - T x), then x = scale * x when `scale` (an (n,) vector) is
+ * non-null, folded into the store of the stage's last SpMV. W and T (NULL
+ * exactly when sweeps = 0) are kry_csr operators of the preconditioner's dtype
+ * created with kry_csr_create_ex(renumber = 0), borrowed like the other
+ * stages; a stage is 1 + 2 sweeps SpMVs. A preconditioner holds either such
+ * stages or solves and scales (KRY_EINVAL otherwise); with them it takes up to
+ * 256 columns, and it owns the blocks between its SpMVs, allocated at the
+ * first apply of a column count. */
 int kry_ilu0_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, int itype, int64_t *info,
                   int32_t *level, int32_t *order, int32_t *launch, int64_t *diag);
+int kry_isai_lower(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,
+                   int dtype, int itype, void *values, int64_t *info);
+int kry_precond_add_isai(kry_precond *P, const kry_csr *W, const kry_csr *T, int32_t sweeps, const kry_vec *scale);
 int kry_ilu0_factor(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,
                     int dtype, int itype, void *values, int64_t *info);
 int kry_precond_create(kry_ctx *ctx, int64_t n, int dtype, kry_precond **out);

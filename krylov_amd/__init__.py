@@ -23,7 +23,7 @@ from .sparse import CsrOperator, as_device_operator, clear_operator_cache
 from .stationary import gauss_seidel, jacobi, richardson, sor, ssor
 from .chebyshev import chebyshev
 from .triangular import TriangularOperator
-from .precond import Ilu0Preconditioner, SsorPreconditioner, multicolor_ordering
+from .precond import Ilu0Preconditioner, SsorPreconditioner, isai, multicolor_ordering
 
 __version__ = "0.1.0"
 
@@ -49,6 +49,7 @@ __all__ = [
     "SsorPreconditioner",
     "Ilu0Preconditioner",
     "multicolor_ordering",
+    "isai",
     "givens",
     "Householder",
     "lartg",

@@ -166,7 +166,7 @@ class Problem:
         for name, op in self.ops.items():
             if not _is_factored(op):
                 continue
-            if self.kpad > 64:
+            if self.kpad > getattr(op, "max_cols", 64):  # 256 with approximate-inverse solves
                 raise NotImplementedError(
                     f"preconditioner {name}: a factorised preconditioner handles at most 64 right-hand-side columns; "
                     "split the block"

@@ -66,6 +66,7 @@ _SIGNATURES = {
     "kry_ctx_synchronize": [_vp],
     "kry_csr_create": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _pvp],
     "kry_csr_destroy": [_vp],
+    "kry_csr_create_ex": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _pvp],
     "kry_csr_create_like": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _pvp],
     "kry_csr_permute": [_vp, _vp, _vp, _vp, _int],
     "kry_csr_compare": [_vp, _vp, _ip64],
@@ -163,6 +164,8 @@ _SIGNATURES = {
     "kry_tri_solve": [_vp, _vp, _vp, _vp],
     "kry_ilu0_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp, _vp, _vp, _vp],
     "kry_ilu0_factor": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _ip64],
+    "kry_isai_lower": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _ip64],
+    "kry_precond_add_isai": [_vp, _vp, _vp, _i32, _vp],
     "kry_precond_create": [_vp, _i64, _int, _pvp],
     "kry_precond_destroy": [_vp],
     "kry_precond_add_tri": [_vp, _vp],

@@ -431,7 +431,7 @@ extern "C" {
 // kry_gmres_xk_device. 107: uniform slot columns of the diagonal-offset image
 // (kry_csr_info_n: two more values; kry_dia_uniform_plan; kry_csr_compare:
 // bits 23-25).
-int kry_version(void) { return 109; }
+int kry_version(void) { return 110; }
 
 #ifndef KRY_BUILD_ID
 #define KRY_BUILD_ID "unknown"
@@ -557,10 +557,14 @@ uint64_t perm_fingerprint(const std::vector<int32_t> &p) {
 // preconditioner of a renumbered operator); otherwise renumber when the
 // columns are scattered and the graph has narrow levels (KRY_RENUMBER=0
 // disables; KRY_RCM_WLIMIT sets the level-width limit, default max(2^16, n / 32)).
+// renumber = false keeps the caller's numbering whatever the matrix looks like
+// (kry_csr_create_ex: the images of a factorised preconditioner's stages).
 template <typename I, typename MV>
-void csr_upload(kry_csr *A, const I *ip, const I *ix, const MV *dv, const std::vector<int32_t> *like_perm) {
+void csr_upload(kry_csr *A, const I *ip, const I *ix, const MV *dv, const std::vector<int32_t> *like_perm,
+                bool renumber) {
   hipStream_t st = A->ctx->stream;
   const int64_t n = A->n, nnz = A->nnz;
+  const bool may_renumber = renumber && !env_off("KRY_RENUMBER");
   UploadTrace tr;
   // the device build (int32 CSR; KRY_DEVICE_BUILD=0: the host builders):
   // 1 = SELL-64 and DIA built on the device, nothing else to do (stencils:
@@ -570,7 +574,7 @@ void csr_upload(kry_csr *A, const I *ip, const I *ix, const MV *dv, const std::v
   if constexpr (sizeof(I) == 4) {
     if (!like_perm && n > 0 && nnz > 0 && !env_off("KRY_DEVICE_BUILD")) {
       DeviceCsrFlags df;
-      dres = device_image_build(A, ip, ix, dv, !env_off("KRY_RENUMBER"), &df);
+      dres = device_image_build(A, ip, ix, dv, may_renumber, &df);
       tr.mark("device build (H2D + SELL-64 + DIA)");
       if (dres == 1) return;
     }
@@ -580,7 +584,7 @@ void csr_upload(kry_csr *A, const I *ip, const I *ix, const MV *dv, const std::v
   const std::vector<int32_t> *perm = like_perm;
   if (perm) {
     KRY_REQUIRE((int64_t)perm->size() == n, KRY_EINVAL, "renumbering of another size");
-  } else if (sizeof(I) == 4 && !env_off("KRY_RENUMBER") && scattered(n, ip, ix)) {
+  } else if (sizeof(I) == 4 && may_renumber && scattered(n, ip, ix)) {
     const char *we = getenv("KRY_RCM_WLIMIT");
     const int64_t wlimit = we ? std::max<int64_t>(1, atoll(we)) : std::max<int64_t>(int64_t(1) << 16, n / 32);
     // on the device (one H2D of indptr / indices; KRY_RCM_DEVICE=0: the host
@@ -795,7 +799,7 @@ static void csr_free(kry_csr *A) {
 extern "C" {
 
 static kry_csr *csr_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices,
-                           const void *data, int dtype, int itype, const kry_csr *like) {
+                           const void *data, int dtype, int itype, const kry_csr *like, bool renumber = true) {
   KRY_REQUIRE(ctx && indptr && (nnz == 0 || (indices && data)), KRY_EINVAL, "null argument");
   KRY_REQUIRE(n >= 0 && nnz >= 0, KRY_EINVAL, "negative size");
   KRY_REQUIRE(dtype == KRY_F32 || dtype == KRY_F64, KRY_EINVAL, "dtype must be f32 or f64");
@@ -818,13 +822,13 @@ static kry_csr *csr_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *ind
     const void *ix = nnz ? indices : (itype == KRY_I32 ? (const void *)&zi32 : (const void *)&zi64);
     const void *dv = nnz ? data : (const void *)&zd;
     if (itype == KRY_I32 && dtype == KRY_F64)
-      csr_upload(A, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(ix), static_cast<const double *>(dv), lp);
+      csr_upload(A, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(ix), static_cast<const double *>(dv), lp, renumber);
     else if (itype == KRY_I32)
-      csr_upload(A, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(ix), static_cast<const float *>(dv), lp);
+      csr_upload(A, static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(ix), static_cast<const float *>(dv), lp, renumber);
     else if (dtype == KRY_F64)
-      csr_upload(A, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(ix), static_cast<const double *>(dv), lp);
+      csr_upload(A, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(ix), static_cast<const double *>(dv), lp, renumber);
     else
-      csr_upload(A, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(ix), static_cast<const float *>(dv), lp);
+      csr_upload(A, static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(ix), static_cast<const float *>(dv), lp, renumber);
   } catch (...) {
     csr_free(A);
     delete A;
@@ -838,6 +842,14 @@ int kry_csr_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, con
   KRY_API_BEGIN
   KRY_REQUIRE(out, KRY_EINVAL, "null argument");
   *out = csr_create(ctx, n, nnz, indptr, indices, data, dtype, itype, nullptr);
+  KRY_API_END
+}
+
+int kry_csr_create_ex(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices,
+                      const void *data, int dtype, int itype, int renumber, kry_csr **out) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(out, KRY_EINVAL, "null argument");
+  *out = csr_create(ctx, n, nnz, indptr, indices, data, dtype, itype, nullptr, renumber != 0);
   KRY_API_END
 }
 

@@ -10,18 +10,31 @@
 
 struct kry_tri;
 
-// A stage is a triangular solve (tri) or a row scale by an (n,) device vector
-// of the preconditioner's dtype (scale). The stages are borrowed: the caller
-// keeps the kry_tri / kry_vec handles alive while the preconditioner is.
+// A stage is a triangular solve (tri), a row scale by an (n,) device vector
+// of the preconditioner's dtype (scale), or an approximate-inverse solve
+// (isai_w): x = W y, then `sweeps` times x = x + W (y - T x), and x = scale * x
+// folded into the last product's store when the stage carries a scale. The
+// stages are borrowed: the caller keeps the kry_tri / kry_vec / kry_csr
+// handles alive while the preconditioner is. A preconditioner holds solves
+// and scales or approximate-inverse stages, never both.
 struct kry_precond {
   struct Stage {
     const kry_tri *tri = nullptr;
     const void *scale = nullptr;
+    const kry_csr *isai_w = nullptr, *isai_t = nullptr;  // isai_t: null without sweeps
+    int sweeps = 0;
   };
   kry_ctx *ctx = nullptr;
   int64_t n = 0;
   int dtype = 0;
   std::vector<Stage> stages;
+  // An SpMV cannot run in place: the blocks the approximate-inverse stages
+  // write between the source and the destination (two that alternate and the
+  // residual of a sweep), n x scratch_k each, allocated at the first apply of
+  // a k larger than any before.
+  mutable void *scratch[3] = {nullptr, nullptr, nullptr};
+  mutable int scratch_k = 0;
+  ~kry_precond();
   // The fused apply of a multicolour object (kry_precond_fuse; precond.hip
   // fuse_plan), one entry per stage. A scale stage with `folded` set launches
   // nothing: the next solve multiplies its right-hand side by it (`pre`). A
@@ -60,6 +73,9 @@ int tri_launches(const kry_tri *T, bool skip_first, bool skip_last);
 // others work in place on dst; dst may alias src)
 void precond_stages(const kry_precond *P, int k, const void *src, void *dst, const Ctrl *ctrl, int step,
                     hipStream_t st);
+// the most columns an apply takes: kMaxCols for approximate-inverse stages
+// (SpMVs), 64 for triangular solves
+int precond_max_cols(const kry_precond *P);
 // what every set_precond of the cores checks
 void precond_check(const kry_precond *P, const kry_csr *A, int64_t n, int k, int dtype);
 // what every set_preconditioners of the cores checks of a matrix it is given

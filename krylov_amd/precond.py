@@ -27,6 +27,17 @@ of thin ones). The vectors stay in the caller's numbering; the apply is bitwise
 the natural-order object built on B, applied to the permuted vector. Such an
 object also folds the row scale into the following solve and fuses the level
 the two solves share into one launch (``KRY_PRECOND_FUSE=0`` turns that off).
+
+``solve="isai"`` replaces each triangular solve by a product with the
+incomplete sparse approximate inverse of its factor (Anzt, Huckle, Braeckle,
+Dongarra): W on the factor T's own pattern with (W T) = I on that pattern
+(``isai``, ``kry_isai_lower``), so a solve is one SpMV, and ``sweeps``
+relaxation steps ``x = x + W (y - T x)`` win back the exact solve's quality.
+The upper factor takes ``W_U = isai(U^T)^T``, the right inverse, so that
+``W_U = W_L^T`` bitwise when ``U = L^T`` and an SSOR object of a symmetric A
+stays symmetric. An apply is ``2 + 4 sweeps`` SpMV launches (SSOR's row scale
+goes into the store of the lower stage's last product) and takes up to 256
+columns; W and T are device matrices that are never renumbered.
 """
 import ctypes
 import time
@@ -106,6 +117,58 @@ def _back(T, rank):
     return T[rank][:, rank].tocsr()
 
 
+def _isai_lower(csr, dt, ctx):
+    """W's values and {"longest", "kernel_seconds"} for a canonical lower
+    triangular CSR (kry_isai_lower)."""
+    n, nnz = csr.shape[0], int(csr.nnz)
+    if nnz >= 2**31 - 1 or n >= 2**31 - 1:
+        raise NotImplementedError("the approximate inverse indexes entries in int32")
+    indptr = np.ascontiguousarray(csr.indptr, dtype=np.int32)
+    indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
+    data = np.ascontiguousarray(csr.data, dtype=dt)
+    vals = np.zeros(max(nnz, 1), dtype=dt)
+    info = np.zeros(3, dtype=np.int64)
+    check(lib.kry_isai_lower(ctx.handle, n, nnz, _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data),
+                             _lib.dtype_code(dt), _lib.KRY_I32, _lib.ptr(vals),
+                             info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+    W = scipy.sparse.csr_matrix((vals[:nnz], indices, indptr), shape=(n, n))
+    return W, {"longest": int(info[1]), "kernel_seconds": float(info[2]) * 1e-6}
+
+
+def isai(T, lower=True, dtype=None, device=None, stats=None):
+    """The incomplete sparse approximate inverse W of a sparse triangular T
+    (scipy.sparse matrix or dense array, on the host) as scipy CSR: W has T's
+    pattern and (W T) = I on it. Row i with pattern J (ending in i) is the
+    back substitution ``T(J, J)^T w = e_last``, computed on the device bitwise
+    as the sequential loop in stored order (``kry_isai_lower``). ``lower=False``:
+    ``isai(T^T)^T``, the right inverse with (T W) = I on T's pattern. Every
+    row of the triangle must store its diagonal; a zero or non-finite diagonal
+    raises ``LinAlgError`` naming the smallest such row, a row of more than
+    1024 entries ``NotImplementedError``, an entry on the wrong side of the
+    diagonal ``ValueError``. ``stats``: a dict that receives "longest" (row)
+    and "kernel_seconds"."""
+    csr, dt = _canonical(T, "isai", dtype)
+    low = csr if lower else csr.T.tocsr()
+    low.sort_indices()
+    W, st = _isai_lower(low, dt, get_context(device))
+    if stats is not None:
+        stats.update(st)
+    if not lower:
+        W = W.T.tocsr()
+        W.sort_indices()
+    return W
+
+
+def _check_solve(solve, sweeps):
+    if solve not in ("exact", "isai"):
+        raise ValueError(f'solve must be "exact" or "isai", not {solve!r}')
+    if int(sweeps) != sweeps or sweeps < 0:
+        raise ValueError(f"sweeps must be an integer >= 0, not {sweeps!r}")
+    if sweeps > 0 and solve == "exact":
+        raise ValueError('sweeps > 0 goes with solve="isai": an exact solve has nothing to relax')
+    return solve, int(sweeps)
+
+
 def refuse_sharded(**ops):
     """The multi-GPU drivers take matrix preconditioners only."""
     for name, op in ops.items():
@@ -123,8 +186,40 @@ class _Factored:
 
     factored = True
     renumbered = False
+    solve_kind = "exact"
+    sweeps = 0
+    max_cols = MAX_COLS  # 256 with solve="isai"
 
-    def _setup(self, n, dt, ctx, stages, ordering="natural", colors=None, perm=None):
+    def _setup_isai(self, n, dt, ctx, lower, upper, scale, sweeps, ordering, colors, perm, rank):
+        """The two approximate-inverse stages of the factors lower / upper
+        (in B's numbering under ordering="multicolor") and SSOR's scale."""
+        t0 = time.perf_counter()
+        st_l, st_u = {}, {}
+        self._W = (isai(lower, True, dtype=dt, device=ctx.device, stats=st_l),
+                   isai(upper, False, dtype=dt, device=ctx.device, stats=st_u))
+        # both kernels alone, and the calls around them (checks, transposes, copies); tools/bench_precond.py
+        self.isai_kernel_seconds = st_l["kernel_seconds"] + st_u["kernel_seconds"]
+        self.isai_seconds = time.perf_counter() - t0
+        self.solve_kind, self.sweeps, self.max_cols = "isai", sweeps, 256
+        t0 = time.perf_counter()
+
+        def image(M):  # in the caller's numbering, which the device keeps
+            M = (M if rank is None else _back(M, rank)).astype(dt)
+            M.sort_indices()
+            return CsrOperator(M, ctx=ctx, renumber=False)
+
+        ws = [image(W) for W in self._W]
+        ts = [image(T) for T in (lower, upper)] if sweeps else [None, None]
+        sv = None if scale is None else DeviceVector.from_host(
+            ctx, (scale if rank is None else scale[rank]).reshape(-1, 1), dtype=dt)
+        self.image_seconds = time.perf_counter() - t0
+        self._begin(n, dt, ctx, ws + ts + [sv], ordering, colors, perm)
+        for W, T, s in ((ws[0], ts[0], sv), (ws[1], ts[1], None)):
+            check(lib.kry_precond_add_isai(self.handle, W.handle, None if T is None else T.handle, sweeps,
+                                           None if s is None else s.handle))
+        self._isai_images = list(zip(ws, ts))
+
+    def _begin(self, n, dt, ctx, stages, ordering, colors, perm):
         self.ordering = ordering
         self.colors = colors  # per row (None in natural order)
         self.perm = perm  # rows by (colour, row): B = A[perm][:, perm]
@@ -137,6 +232,10 @@ class _Factored:
         check(lib.kry_precond_create(ctx.handle, n, _lib.dtype_code(dt), ctypes.byref(h)))
         self.handle = h
         self._fin = _lib.own(self, lib.kry_precond_destroy, h)
+
+    def _setup(self, n, dt, ctx, stages, ordering="natural", colors=None, perm=None):
+        self._begin(n, dt, ctx, stages, ordering, colors, perm)
+        h = self.handle
         for s in stages:
             if isinstance(s, TriangularOperator):
                 check(lib.kry_precond_add_tri(h, s.handle))
@@ -155,18 +254,28 @@ class _Factored:
         "colors" and "color_sizes" (the number of colours and the rows of each;
         None in natural order); "launches": kernel launches per apply;
         "fused": whether the apply folds the scale into the following solve and
-        fuses matching level boundaries (kry_precond_info)}."""
+        fuses matching level boundaries (kry_precond_info); "solve" ("exact" or
+        "isai") and "sweeps"}. With solve="isai" a stage is {"isai": W's device
+        image (CsrOperator.layout), "triangle": T's (None without sweeps),
+        "sweeps", "scale": whether the row scale rides on its last store}, and
+        "launches" counts the SpMVs: 2 + 4 sweeps."""
         info = np.zeros(5, dtype=np.int64)
         check(lib.kry_precond_info(self.handle, info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         sizes = None if self.colors is None else [int(c) for c in np.bincount(self.colors)]
-        return {"stages": [s.layout() if isinstance(s, TriangularOperator) else {"scale": self.n}
-                           for s in self._stages],
+        if self.solve_kind == "isai":
+            stages = [{"isai": W.layout(), "triangle": None if T is None else T.layout(), "sweeps": self.sweeps,
+                       "scale": i == 0 and self._stages[-1] is not None}
+                      for i, (W, T) in enumerate(self._isai_images)]
+        else:
+            stages = [s.layout() if isinstance(s, TriangularOperator) else {"scale": self.n} for s in self._stages]
+        return {"stages": stages, "solve": self.solve_kind, "sweeps": self.sweeps,
                 "ordering": self.ordering, "colors": None if sizes is None else len(sizes), "color_sizes": sizes,
                 "launches": int(info[0]), "fused": bool(info[1])}
 
     def matvec_device(self, x, y):
-        """y = P x for DeviceVectors (n x k, k a power of two <= 64, this
-        preconditioner's dtype) in the caller's numbering; y may be x."""
+        """y = P x for DeviceVectors (n x k, k a power of two <= 64, 256 with
+        solve="isai", this preconditioner's dtype) in the caller's numbering;
+        y may be x."""
         check(lib.kry_precond_apply(self.ctx.handle, self.handle, x.handle, y.handle))
 
     matvec_op = matvec_device  # never renumbered
@@ -179,8 +288,10 @@ class _Factored:
         y2 = np.ascontiguousarray(y.reshape(self.n, -1), dtype=self.dtype)
         k = y2.shape[1]
         kp = _next_pow2(k)
-        if kp > MAX_COLS:
-            raise NotImplementedError("at most 64 right-hand-side columns on a factorised preconditioner")
+        if kp > self.max_cols:
+            raise NotImplementedError(
+                f"at most {self.max_cols} right-hand-side columns on a factorised preconditioner"
+                + ("" if self.max_cols > MAX_COLS else ' (256 with solve="isai")'))
         if kp != k:
             y2 = np.concatenate([y2, np.zeros((self.n, kp - k), dtype=self.dtype)], axis=1)
         yv = DeviceVector(self.ctx, self.n, kp, self.dtype)
@@ -190,6 +301,14 @@ class _Factored:
         return np.ascontiguousarray(xv.to_host()[:, :k]).reshape(y.shape)
 
     __matmul__ = solve
+
+    def inverses(self):
+        """(W_L, W_U) as scipy CSR with solve="isai": the approximate inverses
+        of the two factors on the factors' patterns, (W_L L) = I on L's and
+        (U W_U) = I on U's, in the numbering of ``factors()``."""
+        if self.solve_kind != "isai":
+            raise ValueError('inverses() goes with solve="isai": this object solves its factors exactly')
+        return self._W
 
     def close(self):
         self._fin()
@@ -204,9 +323,12 @@ class SsorPreconditioner(_Factored):
     a preconditioner). ``A``: scipy.sparse matrix or dense array; ``dtype``:
     the dtype of the vectors it will precondition (default A's).
     ``ordering="multicolor"``: L and U split the off-diagonal entries by the
-    multicolour elimination order instead of by index (the module's notes)."""
+    multicolour elimination order instead of by index (the module's notes).
+    ``solve="isai"``: each solve is a product with the factor's approximate
+    inverse and ``sweeps`` relaxation steps (the module's notes)."""
 
-    def __init__(self, A, omega=1.0, dtype=None, device=None, ordering="natural"):
+    def __init__(self, A, omega=1.0, dtype=None, device=None, ordering="natural", solve="exact", sweeps=0):
+        solve, sweeps = _check_solve(solve, sweeps)
         csr, dt = _canonical(A, "SsorPreconditioner", dtype)
         colors, perm, rank, B = _ordering(csr, ordering)
         n = csr.shape[0]
@@ -222,6 +344,9 @@ class SsorPreconditioner(_Factored):
         self._upper = (scipy.sparse.triu(csr, 1) + diag).tocsr().astype(dt)
         self._scale = (d * dt.type((2 - omega) / omega)).astype(dt)
         ctx = get_context(device)
+        if solve == "isai":
+            self._setup_isai(n, dt, ctx, self._lower, self._upper, self._scale, sweeps, ordering, colors, perm, rank)
+            return
         if B is None:
             lo, up, scale = self._lower, self._upper, self._scale
         else:  # the same factors in the caller's numbering, solved in the order perm lists the rows in
@@ -244,9 +369,12 @@ class Ilu0Preconditioner(_Factored):
     a pivot that comes out zero or non-finite raises ``LinAlgError`` naming the
     row. ``ordering="multicolor"``: the factors of B = A[perm][:, perm] (the
     module's notes); ``lu`` and ``factors()`` are then in B's numbering, and so
-    is the row an error names."""
+    is the row an error names. ``solve="isai"``: each solve is a product with
+    the factor's approximate inverse and ``sweeps`` relaxation steps (the
+    module's notes)."""
 
-    def __init__(self, A, dtype=None, device=None, ordering="natural"):
+    def __init__(self, A, dtype=None, device=None, ordering="natural", solve="exact", sweeps=0):
+        solve, sweeps = _check_solve(solve, sweeps)
         csr, dt = _canonical(A, "Ilu0Preconditioner", dtype)
         colors, perm, rank, B = _ordering(csr, ordering)
         if B is not None:
@@ -279,6 +407,9 @@ class Ilu0Preconditioner(_Factored):
         self._U = scipy.sparse.coo_matrix((vals[~low], (rows[~low], indices[~low])), shape=(n, n)).tocsr()
         self._L.sort_indices()
         self._U.sort_indices()
+        if solve == "isai":
+            self._setup_isai(n, dt, ctx, self._L, self._U, None, sweeps, ordering, colors, perm, rank)
+            return
         lo, up = (self._L, self._U) if B is None else (_back(self._L, rank), _back(self._U, rank))
         self._setup(n, dt, ctx, [TriangularOperator(lo, lower=True, ctx=ctx, dtype=dt, order=perm),
                                  TriangularOperator(up, lower=False, ctx=ctx, dtype=dt, order=perm)],

@@ -32,9 +32,11 @@ class CsrOperator:
     matrices with a narrow level structure). Vectors always cross in the
     caller's numbering. ``ctx``: a ``device.Context`` to build it on instead
     of the device's shared one (its own stream; e.g. two solves driven
-    concurrently on one GPU)."""
+    concurrently on one GPU). ``renumber=False``: the image keeps the caller's
+    numbering whatever the matrix looks like (kry_csr_create_ex; the matrices
+    of a factorised preconditioner's approximate-inverse stages)."""
 
-    def __init__(self, A, device=None, like=None, ctx=None):
+    def __init__(self, A, device=None, like=None, ctx=None, renumber=True):
         if isinstance(A, CsrOperator):
             raise TypeError("already a CsrOperator")
         if scipy.sparse.issparse(A):
@@ -66,6 +68,8 @@ class CsrOperator:
         data = np.ascontiguousarray(csr.data, dtype=dt)
         self.index_dtype = np.dtype(itype)
         h = ctypes.c_void_p()
+        if like is not None and like.renumbered and not renumber:
+            raise ValueError("renumber=False and a renumbered `like` contradict each other")
         if like is not None and like.renumbered:
             if like.ctx is not self.ctx or like.n != self.n:
                 raise ValueError("like: an operator of the same size on the same device")
@@ -73,6 +77,13 @@ class CsrOperator:
                 lib.kry_csr_create_like(
                     self.ctx.handle, like.handle, self.n, self.nnz, _lib.ptr(indptr), _lib.ptr(indices),
                     _lib.ptr(data), _lib.dtype_code(dt), _lib.itype_code(itype), ctypes.byref(h),
+                )
+            )
+        elif not renumber:
+            check(
+                lib.kry_csr_create_ex(
+                    self.ctx.handle, self.n, self.nnz, _lib.ptr(indptr), _lib.ptr(indices),
+                    _lib.ptr(data), _lib.dtype_code(dt), _lib.itype_code(itype), 0, ctypes.byref(h),
                 )
             )
         else:

@@ -7,11 +7,18 @@ Ilu0Preconditioner) as one JSON line.
 Workloads: poisson2d(1000) (SPD, 1,999 thin levels) and
 random_nonsym(2_000_000) (nonsymmetric, fat levels), b = ones. Every
 preconditioner runs in natural order (ssor, ilu0) and in the multicolour order
-(ssor_mc, ilu0_mc: ordering="multicolor") in the same run. Per workload and
-preconditioner:
+(ssor_mc, ilu0_mc: ordering="multicolor") in the same run, and in natural order
+with its two solves replaced by approximate-inverse products (solve="isai")
+without and with one relaxation sweep (ssor_isai, ssor_isai_s1, ilu0_isai,
+ilu0_isai_s1). Per workload: spmv_ms, one A x on a device vector, timed like an
+apply. Per workload and preconditioner:
   setup_s        the constructor, whole (host analysis, uploads, images)
   factor_s       ILU(0) only: kry_ilu0_factor (analysis, upload, the
                  factorisation kernels, the values' way back)
+  isai_s, isai_kernel_s, image_s   solve="isai" only: the two krylov_amd.isai
+                 calls (checks, transposes, upload, kernel, the values' way
+                 back), of that the two kry_isai_lower kernels alone (HIP
+                 events), and the device images of W (and T with sweeps)
   ms_per_apply   one P r on a device vector (k = 1): HIP events around a
                  region of back-to-back applies (5, or as many as fill 20 ms),
                  median of REGIONS regions
@@ -48,6 +55,7 @@ def median(v):
 
 
 def time_apply(P):
+    """P: a preconditioner or a CsrOperator (the SpMV beside the applies)."""
     from krylov_amd.device import DeviceVector
 
     y = DeviceVector.from_host(P.ctx, np.ones((P.n, 1)), dtype=P.dtype)
@@ -73,11 +81,19 @@ def build(name, make):
     out = {"setup_s": time.perf_counter() - t0}
     if hasattr(P, "factor_seconds"):
         out["factor_s"] = P.factor_seconds
+    if hasattr(P, "isai_seconds"):
+        out["isai_s"], out["isai_kernel_s"], out["image_s"] = P.isai_seconds, P.isai_kernel_seconds, P.image_seconds
     out["ms_per_apply"], out["ms_regions"] = time_apply(P)
     lay = P.layout()
     if "factor" in lay:
         out["factor_plan"] = lay["factor"]
-    out["stages"] = [{k: s[k] for k in ("levels", "launches") if k in s} or s for s in lay["stages"]]
+    if lay["solve"] == "isai":
+        out["stages"] = [{"sweeps": s["sweeps"], "scale": s["scale"],
+                          "image": [k for k in ("dia", "col_blocks", "pair", "rs") if s["isai"][k]]}
+                         for s in lay["stages"]]
+    else:
+        out["stages"] = [{k: s[k] for k in ("levels", "launches") if k in s} or s for s in lay["stages"]]
+    out["solve"], out["sweeps"] = lay["solve"], lay["sweeps"]
     out["launches"], out["fused"], out["colors"] = lay["launches"], lay["fused"], lay["colors"]
     print(f"  {name}: setup {out['setup_s']:.2f} s, apply {out['ms_per_apply']:.3f} ms", file=sys.stderr, flush=True)
     return P, out
@@ -112,10 +128,16 @@ def workload(name, A, spd):
     b = np.ones(n)
     out = {"n": n, "nnz": int(A.nnz), "precond": {}, "solves": {}}
     precs = {"none": None}
+    out["spmv_ms"], _ = time_apply(krylov_amd.as_device_operator(A))
+    isai = {"solve": "isai"}
     for pname, make in (("ssor", lambda: krylov_amd.SsorPreconditioner(A, omega=1.0)),
                         ("ilu0", lambda: krylov_amd.Ilu0Preconditioner(A)),
                         ("ssor_mc", lambda: krylov_amd.SsorPreconditioner(A, omega=1.0, ordering="multicolor")),
-                        ("ilu0_mc", lambda: krylov_amd.Ilu0Preconditioner(A, ordering="multicolor"))):
+                        ("ilu0_mc", lambda: krylov_amd.Ilu0Preconditioner(A, ordering="multicolor")),
+                        ("ssor_isai", lambda: krylov_amd.SsorPreconditioner(A, omega=1.0, **isai)),
+                        ("ssor_isai_s1", lambda: krylov_amd.SsorPreconditioner(A, omega=1.0, sweeps=1, **isai)),
+                        ("ilu0_isai", lambda: krylov_amd.Ilu0Preconditioner(A, **isai)),
+                        ("ilu0_isai_s1", lambda: krylov_amd.Ilu0Preconditioner(A, sweeps=1, **isai))):
         try:
             precs[pname], out["precond"][pname] = build(pname, make)
         except Exception as e:  # recorded, not hidden: e.g. a singular pivot
