@@ -231,7 +231,12 @@ int kry_cb_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices,
  * diagonal-offset image (0 with KRY_DIA_UNIFORM=0) and the bytes of matrix
  * values the single-RHS kernel still streams per SpMV: (slot columns -
  * uniform ones) * 128 * the value size. */
-#define KRY_CSR_INFO_LEN 15
+/* then (kry_version() >= 111) dia_lean: 1 when the single-RHS kernel of the
+ * diagonal-offset image loads x at 32-bit byte offsets through a buffer
+ * descriptor (the default while (n + 2) * 8 bytes fit it), 0 when it forms
+ * per-lane 64-bit addresses (KRY_DIA_LEAN=0, or a larger n) or there is no
+ * such image. */
+#define KRY_CSR_INFO_LEN 16
 int kry_csr_info_n(const kry_csr *A, int64_t *info, int32_t len);
 /* The version-100 form: info[0..4] only (`info` holds 5 values). */
 int kry_csr_info(const kry_csr *A, int64_t *info);

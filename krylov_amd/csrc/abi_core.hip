@@ -430,8 +430,8 @@ extern "C" {
 // (CG total_k + 1, GMRES / MINRES total_k + 2 values); kry_cg_defer_info,
 // kry_gmres_xk_device. 107: uniform slot columns of the diagonal-offset image
 // (kry_csr_info_n: two more values; kry_dia_uniform_plan; kry_csr_compare:
-// bits 23-25).
-int kry_version(void) { return 110; }
+// bits 23-25). 111: kry_csr_info_n reports the lean diagonal-offset kernel.
+int kry_version(void) { return 111; }
 
 #ifndef KRY_BUILD_ID
 #define KRY_BUILD_ID "unknown"
@@ -515,7 +515,8 @@ int kry_csr_info_n(const kry_csr *A, int64_t *info, int32_t len) {
                                          A->rcm_levels, A->dia ? A->dia_nuniform : 0,
                                          A->dia ? (A->dia_nslots / kDiaSlice - A->dia_nuniform) * kDiaSlice *
                                                       (int64_t)dsize(A->dtype)
-                                                : 0};
+                                                : 0,
+                                         A->dia && dia_lean_on(A) ? 1 : 0};
   for (int i = 0; i < len && i < KRY_CSR_INFO_LEN; ++i) info[i] = all[i];
   KRY_API_END
 }

@@ -97,6 +97,42 @@ __device__ __forceinline__ void pstore(V *p, const V (&o)[2]) {
   if (NT) __builtin_nontemporal_store(t, reinterpret_cast<typename PairT<V>::T *>(p));
   else *reinterpret_cast<typename PairT<V>::T *>(p) = t;
 }
+// The pair x[j], x[j + 1] through a raw buffer descriptor over x[-1, n + 1)
+// (the lean diagonal-offset SpMV): the descriptor starts one element before x
+// and ends one element behind it, both inside the allocation slack, so a pair
+// with one element in [0, n) is read whole, as pload reads it; the byte offset
+// of the pair at j is xpair_byte<V>(j), taken modulo 2^32. The range check
+// covers the whole per-lane offset (it is passed as the vector offset; the
+// scalar offset operand is not checked on gfx9), so a pair whose offset lies
+// outside the descriptor touches no memory and reads as 0, and one whose
+// offset wrapped back into it reads mapped elements of x: both belong to
+// lanes whose mask bits are clear. (n + 2) * sizeof(V) must fit 32 bits
+// (kDiaLeanMaxBytes).
+template <typename V>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t xpair_rsrc(const V *x, int64_t n) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<V *>(x) - 1, 0, (int)(uint32_t)((n + 2) * (int64_t)sizeof(V)),
+                                           0x00020000);
+}
+template <typename V>
+__device__ __forceinline__ int xpair_byte(int64_t j) {
+  return (int)((uint32_t)(j + 1) * (uint32_t)sizeof(V));
+}
+template <typename V>
+__device__ __forceinline__ void xpair_load(__amdgpu_buffer_rsrc_t r, int byte, V (&o)[2]) {
+  if constexpr (sizeof(V) == 8) {
+    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const d2 t = __builtin_bit_cast(d2, (u4)__builtin_amdgcn_raw_buffer_load_b128(r, byte, 0, 0));
+    o[0] = t.x;
+    o[1] = t.y;
+  } else {
+    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const f2 t = __builtin_bit_cast(f2, (u2)__builtin_amdgcn_raw_buffer_load_b64(r, byte, 0, 0));
+    o[0] = t.x;
+    o[1] = t.y;
+  }
+}
 // dot terms of two consecutive rows i, i + 1 (one column), summed in order
 __device__ __forceinline__ double dterm2(const double *w, int64_t i, double x0, double y0, double x1, double y1) {
   if (w) return dterm_w(x0, w[i], y0) + dterm_w(x1, w[i + 1], y1);
@@ -123,6 +159,11 @@ struct SrcPlain {
     __device__ __forceinline__ void row(int64_t j, V (&o)[KT]) const { vload_row<V, KT>(x + j * k + c0, o); }
     // rows j and j + 1 of a single column (k = 1, diagonal-offset kernel)
     __device__ __forceinline__ void pair(int64_t j, V (&o)[2]) const { pload<V>(x + j, o); }
+    // the same pair through a bounds-checked descriptor (xpair_rsrc, xpair_load)
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t pair_rsrc(int64_t n) const { return xpair_rsrc<V>(x, n); }
+    __device__ __forceinline__ void pair_at(__amdgpu_buffer_rsrc_t r, int byte, V (&o)[2]) const {
+      xpair_load<V>(r, byte, o);
+    }
   };
   template <int KT>
   __device__ __forceinline__ Bound<KT> bind(int c0) const {
@@ -146,6 +187,12 @@ struct SrcScaled {
     __device__ __forceinline__ V operator()(int64_t j, int c) const { return w[j * k + c0 + c] / h[c]; }
     __device__ __forceinline__ void pair(int64_t j, V (&o)[2]) const {
       pload<V>(w + j, o);
+      o[0] = o[0] / h[0];
+      o[1] = o[1] / h[0];
+    }
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t pair_rsrc(int64_t n) const { return xpair_rsrc<V>(w, n); }
+    __device__ __forceinline__ void pair_at(__amdgpu_buffer_rsrc_t r, int byte, V (&o)[2]) const {
+      xpair_load<V>(r, byte, o);
       o[0] = o[0] / h[0];
       o[1] = o[1] / h[0];
     }
@@ -577,7 +624,15 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(
 // no flag, so far fewer registers than the general kernel and more resident
 // waves: with the matrix stream gone the kernel waits on each slice's chain
 // descriptors -> x loads -> store, not on HBM.
-template <typename V, typename MV, int UNR, class Src, class Epi, int UNI = 1>
+// LEAN (launch_spmv: the default while the vector fits a 32-bit byte offset,
+// dia_lean_on): the two lane masks of a slot column, 64-bit words in scalar
+// registers, are used as the selects' masks directly instead of being tested
+// per lane, and x is loaded through a bounds-checked buffer descriptor at a
+// scalar byte offset per slot column (xpair_rsrc), so a masked-off lane needs
+// no address of its own: per slot column one address add, two products, two
+// adds and the selects. The same loads for present lanes, the same products,
+// adds and selects: the same bits.
+template <typename V, typename MV, int UNR, class Src, class Epi, int UNI = 1, bool LEAN = false>
 __global__ __launch_bounds__(kBlock) void spmv_dia_kernel(const int64_t *__restrict__ sptr,
                                                           const int *__restrict__ swidth,
                                                           const int *__restrict__ doff,
@@ -597,6 +652,9 @@ __global__ __launch_bounds__(kBlock) void spmv_dia_kernel(const int64_t *__restr
   const int64_t m = (int64_t)g * 4 + wid;
   const int64_t s_begin = nslices * m / W, s_end = nslices * (m + 1) / W;
   const auto bs = src.template bind<1>(0);
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t xr;
+  if constexpr (LEAN) xr = bs.pair_rsrc(n);
+  [[maybe_unused]] const int lbyte = lane * 2 * (int)sizeof(V);
   double dacc = 0.0;
   // The epilogue (result store, dot term) of slice s - 1 runs after slice s's
   // first round of loads is issued: on gfx9's in-order vmcnt a wait on those
@@ -664,9 +722,18 @@ __global__ __launch_bounds__(kBlock) void spmv_dia_kernel(const int64_t *__restr
       V xv[UNR][2];
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
-        on0[u] = j0 + u < w && ((me[u] >> lane) & 1u) != 0;
-        on1[u] = j0 + u < w && ((md[u] >> lane) & 1u) != 0;
-        bs.pair((on0[u] || on1[u]) ? row + off[u] : 0, xv[u]);
+        if constexpr (LEAN) {
+          // the masks, zeroed past the slice's width by a scalar select, are
+          // the selects' lane masks as they stand; every lane loads its pair
+          // at the slot column's scalar byte offset plus its own
+          on0[u] = __builtin_amdgcn_inverse_ballot_w64(j0 + u < w ? me[u] : 0);
+          on1[u] = __builtin_amdgcn_inverse_ballot_w64(j0 + u < w ? md[u] : 0);
+          bs.pair_at(xr, xpair_byte<V>(s * kDiaSlice + off[u]) + lbyte, xv[u]);
+        } else {
+          on0[u] = j0 + u < w && ((me[u] >> lane) & 1u) != 0;
+          on1[u] = j0 + u < w && ((md[u] >> lane) & 1u) != 0;
+          bs.pair((on0[u] || on1[u]) ? row + off[u] : 0, xv[u]);
+        }
       }
       if (j0 == 0 && prow >= 0) {  // the previous slice's epilogue, behind this round's loads
         __builtin_amdgcn_sched_barrier(0);
@@ -1634,6 +1701,23 @@ inline int rs1_on() {
   return e ? atoi(e) : 2;
 }
 
+// The lean diagonal-offset kernel (spmv_dia_kernel<..., LEAN = true>) loads x
+// at 32-bit byte offsets into a descriptor over x[-1, n + 1): an operator
+// takes it while n + 2 elements of the widest vector type (8 bytes) stay
+// within kDiaLeanMaxBytes, and the kernel with per-lane 64-bit addresses
+// beyond. KRY_DIA_LEAN=0: that kernel for every operator (A/B and tests);
+// KRY_DIA_LEAN_MAX_BYTES lowers the limit (tests: the fallback at a small n).
+// Both are read at the operator's first use; kry_csr_info_n reports the choice.
+constexpr int64_t kDiaLeanMaxBytes = 0xFFFF0000LL;
+inline bool dia_lean_on(const kry_csr *A) {
+  if (A->dia_lean < 0) {
+    const char *e = getenv("KRY_DIA_LEAN"), *m = getenv("KRY_DIA_LEAN_MAX_BYTES");
+    const int64_t cap = m ? std::min<int64_t>(kDiaLeanMaxBytes, atoll(m)) : kDiaLeanMaxBytes;
+    A->dia_lean = !(e && atoi(e) == 0) && (A->n + 2) * 8 <= cap ? 1 : 0;
+  }
+  return A->dia_lean == 1;
+}
+
 template <typename I>
 inline bool spmv_column_blocked(const kry_csr *A, int k) {
   return sizeof(I) == 4 && k == 1 && !A->dia && A->cb_nb > 0;
@@ -1693,12 +1777,14 @@ void launch_spmv(const kry_csr *A, int k, Src src, Epi epi, double *part, int *g
       // columns, fp32 values) the larger grid measured 1.8 % slower per
       // MINRES iteration, its consumers summing twice the partials.
       // A wide image whose slot columns are all uniform streams no matrix
-      // values: its kernel (UNI = 2, 74 VGPRs, 6 waves per SIMD) waits on each
+      // values: its kernel (UNI = 2: 74 VGPRs, lean 55) waits on each
       // slice's chain of descriptor, x and store latencies, and a wave that
       // walks several slices overlaps one slice's epilogue with the next one's
       // loads. Metric CG, ms per iteration by cap: 19683 (one slice per wave)
       // 0.180, 8192 0.167, 6144 0.165, 5120 0.161, 4096 0.162, 3072 0.168,
-      // 2048 0.178 (profiles/dia_uniform_ab.md).
+      // 2048 0.178 (profiles/dia_uniform_ab.md). The lean kernel (55 VGPRs)
+      // keeps the cap: 3072 0.164, 4096 0.154, 5120 0.152, 6144 0.153, 8192
+      // 0.156, and 16 slot columns per round 0.155 (profiles/dia_lean_ab.md).
       static const int dia_cap_env = [] {
         const char *e = getenv("KRY_DIA_GRID");  // tuning override: grid cap
         return e ? std::max(1, std::min(atoi(e), kMaxGridBlk)) : 0;
@@ -1720,7 +1806,13 @@ void launch_spmv(const kry_csr *A, int k, Src src, Epi epi, double *part, int *g
       // all uniform: 8 slot columns per round also for wide images (16 per
       // round: 104 VGPRs, 4 waves per SIMD, metric CG 0.200 against 0.180 ms
       // per iteration at one slice per wave)
-      if (allu) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 2>);
+      if (dia_lean_on(A)) {
+        if (allu) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 2, true>);
+        else if (A->dia_nuniform == 0 && A->dia_max_width <= 8) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 0, true>);
+        else if (A->dia_nuniform == 0) go(spmv_dia_kernel<V, MV, 16, Src, Epi, 0, true>);
+        else if (A->dia_max_width <= 8) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 1, true>);
+        else go(spmv_dia_kernel<V, MV, 16, Src, Epi, 1, true>);
+      } else if (allu) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 2>);
       else if (A->dia_nuniform == 0 && A->dia_max_width <= 8) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 0>);
       else if (A->dia_nuniform == 0) go(spmv_dia_kernel<V, MV, 16, Src, Epi, 0>);
       else if (A->dia_max_width <= 8) go(spmv_dia_kernel<V, MV, 8, Src, Epi, 1>);

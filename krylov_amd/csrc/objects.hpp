@@ -89,6 +89,10 @@ struct kry_csr {
   int64_t dia_nuniform = 0;   // flagged slot columns
   void *dia_uflag = nullptr;  // int32, dia_nslots / kDiaSlice (+ kDiaPad): 1 = uniform
   void *dia_uval = nullptr;   // dtype, dia_nslots / kDiaSlice (+ kDiaPad): the value, 0 when not flagged
+  // the k = 1 kernel's x loads: 1 = 32-bit offsets into a buffer descriptor
+  // (the lean kernel), 0 = per-lane 64-bit addresses; -1 = not chosen yet
+  // (device.hpp dia_lean_on, at the operator's first use)
+  mutable int dia_lean = -1;
   // paired-row SELL-128 image (general matrices, k = 1; spmv_pair_kernel):
   // slice s covers rows [128 s, 128 s + 128); slot column j of the slice
   // holds the j-th stored entry of every row, row r at position r - 128 s,

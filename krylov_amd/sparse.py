@@ -105,16 +105,18 @@ class CsrOperator:
         """The device image: {"slices", "slots", "irregular", "compact",
         "col_blocks", "dia", "dia_slots", "pair", "pair_slots", "rs",
         "rs_slots", "renumbered", "rcm_levels", "dia_uniform_cols",
-        "dia_value_bytes"} (kry_csr_info_n). The last two: the slot columns of
-        the diagonal-offset image whose value the single-RHS SpMV reads from
-        its descriptor, and the matrix-value bytes it still streams."""
-        info = np.zeros(15, dtype=np.int64)
-        check(lib.kry_csr_info_n(self.handle, info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 15))
+        "dia_value_bytes", "dia_lean"} (kry_csr_info_n). The last three: the
+        slot columns of the diagonal-offset image whose value the single-RHS
+        SpMV reads from its descriptor, the matrix-value bytes it still
+        streams, and whether it loads x through a buffer descriptor (the lean
+        kernel; False with KRY_DIA_LEAN=0 or beyond its size limit)."""
+        info = np.zeros(16, dtype=np.int64)
+        check(lib.kry_csr_info_n(self.handle, info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 16))
         return {"slices": int(info[0]), "slots": int(info[1]), "irregular": int(info[2]), "compact": bool(info[3]),
                 "col_blocks": int(info[4]), "dia": bool(info[5]), "dia_slots": int(info[6]), "pair": bool(info[7]),
                 "pair_slots": int(info[8]), "rs": bool(info[9]), "rs_slots": int(info[10]),
                 "renumbered": bool(info[11]), "rcm_levels": int(info[12]), "dia_uniform_cols": int(info[13]),
-                "dia_value_bytes": int(info[14])}
+                "dia_value_bytes": int(info[14]), "dia_lean": bool(info[15])}
 
     def matvec_device(self, x, y):
         """y = A x for DeviceVectors in the caller's numbering (no host traffic)."""
