@@ -204,9 +204,10 @@ class Problem:
         out[: self.kc] = v
         return out
 
-    def colvals(self, row):
-        """kpad device values -> the reference's per-step scalar/array."""
-        v = np.asarray(row[: self.kc], dtype=np.float64).astype(self.inner_dtype)
+    def colvals(self, row, dtype=None):
+        """kpad device values -> the reference's per-step scalar/array, in the
+        inner products' dtype or in ``dtype``."""
+        v = np.asarray(row[: self.kc], dtype=np.float64).astype(self.inner_dtype if dtype is None else dtype)
         if len(self.tail) == 0:
             return v[0]
         return v.reshape(self.tail)

@@ -96,8 +96,12 @@ def minres(A, b, M=None, Ml=None, Mr=None, inner=None, x0=None, tol=1e-5, atol=1
         callback(prob.x0_or_zeros(), np.array(first))
     criterion = np.maximum(tol * first, atol)
     st.set_criterion(prob.pad_cols(criterion, np.inf))
+    # a step's entry is |y[0]| of the QR recurrence, which the reference keeps
+    # in float64 whatever the vectors' dtype (minres.py:195,219); only the
+    # first entry and the explicit residual are norms in the vectors' dtype
     success, k, resnorms = stop_rule_loop(
-        first, criterion, maxiter, lambda _k, steps: (st.run(steps)[0], None), entry=prob.colvals,
+        first, criterion, maxiter, lambda _k, steps: (st.run(steps)[0], None),
+        entry=lambda row: prob.colvals(row, np.float64),
         chunk=1 if callback is not None else _helpers.CHUNK, recheck=lambda: prob.colnorms(st.residual_norm2()),
         on_chunk=None if callback is None else lambda _k, rn: callback(st.xk(), np.array(rn)))
     xk = st.xk(out=host_out.take())

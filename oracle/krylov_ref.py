@@ -21,7 +21,8 @@ SciPy ``csr_matvec``/``csr_matvecs`` (``A @ x``), 1-D inner products to
 column), rotations to LAPACK ``dlartg``. Parity pinned: every function here is
 checked against fixtures produced by the reference itself
 (``tests/golden/make_golden.py`` → ``tests/golden/solvers.npz``) in
-``tests/test_oracle.py``.
+``tests/test_oracle.py``; unweighted float32 runs of ``cg``, ``gmres`` and
+``minres`` by ``tests/golden/make_f32.py`` → ``tests/golden/f32.npz``.
 """
 from collections import namedtuple
 
@@ -164,13 +165,20 @@ def _trisolve_columns(R, y):
 
 
 class _House:
-    """householder.py:6-65 (real case): H x = alpha ||x|| e_1."""
+    """householder.py:6-65 (real case): H x = alpha ||x|| e_1.
 
-    def __init__(self, x):
+    ``dot`` (test hook): another evaluation of the reflector's Euclidean inner
+    product (householder.py:24), for measuring what its summation order moves;
+    None is the reference's own."""
+
+    def __init__(self, x, dot=None):
         v = x.copy()
         gamma = v[0].copy()
         v[0] = 1
-        sigma2 = np.dot(v[1:].conj(), v[1:]) if v.ndim == 1 else np.einsum("i...,i...->...", v[1:].conj(), v[1:])
+        if dot is not None:
+            sigma2 = dot(v[1:], v[1:])
+        else:
+            sigma2 = np.dot(v[1:].conj(), v[1:]) if v.ndim == 1 else np.einsum("i...,i...->...", v[1:].conj(), v[1:])
         xnorm = np.sqrt(np.abs(gamma) ** 2 + sigma2)
         if sigma2 == 0:
             beta = 0
@@ -187,7 +195,7 @@ class _House:
         self.v = v / np.sqrt(np.abs(v[0]) ** 2 + sigma2)
         self.alpha = alpha
         self.beta = beta
-        self.inner = default_inner(x.shape)
+        self.inner = default_inner(x.shape) if dot is None else dot
 
     def __matmul__(self, x):
         if self.beta == 0:
@@ -196,15 +204,17 @@ class _House:
 
 
 class _ArnoldiHouseholder:
-    """arnoldi.py:33-104."""
+    """arnoldi.py:33-104. ``dot``: the test hook of ``_House``, which also
+    stands in for the norm of the start vector."""
 
-    def __init__(self, A, v):
+    def __init__(self, A, v, dot=None):
         self.A = A
         self.v = v
+        self.dot = dot
         self.iter = 0
         self.is_invariant = False
-        self.houses = [_House(v)]
-        vnorm = np.linalg.norm(v, 2)
+        self.houses = [_House(v, dot)]
+        vnorm = np.linalg.norm(v, 2) if dot is None else np.sqrt(dot(v, v))
         self.V = [v / np.where(vnorm != 0.0, vnorm, 1.0)]
 
     def __next__(self):
@@ -217,7 +227,7 @@ class _ArnoldiHouseholder:
             Av[j] *= np.conj(self.houses[j].alpha)
         N = self.v.shape[0]
         if k < N - 1:
-            house = _House(Av[k + 1:])
+            house = _House(Av[k + 1:], self.dot)
             self.houses.append(house)
             Av[k + 1:] = (house @ Av[k + 1:]) * np.conj(house.alpha)
             h = Av[: k + 2]
@@ -246,9 +256,13 @@ def _ident(v):
 
 
 def gmres(A, b, inner=None, ortho="mgs", x0=None, tol=1e-5, atol=1e-15, maxiter=None, callback=None, M=None,
-          Ml=None, Mr=None, shard=None):
+          Ml=None, Mr=None, shard=None, house_dot=None):
     """Restates gmres.py:41-251 with Arnoldi MGS (arnoldi.py:107-200) or
     Householder (arnoldi.py:33-104).
+
+    ``house_dot`` (test hook): the inner product of the Householder
+    reflectors, which ``inner`` does not reach (householder.py:24 takes the
+    default one); None is the reference's own.
 
     ``shard`` (test hook for the RHS-sharded path): a callable
     mapping this rank's per-column values to the global column vector (all
@@ -284,7 +298,7 @@ def gmres(A, b, inner=None, ortho="mgs", x0=None, tol=1e-5, atol=1e-15, maxiter=
     V = [M_Ml_r0 / np.where(r0norm != 0.0, r0norm, 1.0)]
     if house:  # ArnoldiHouseholder(Ml_A_Mr, Ml_r0) (gmres.py:158-161)
         op = _Prod(Ml, A, Mr)
-        hh = _ArnoldiHouseholder(op, Ml_r0)
+        hh = _ArnoldiHouseholder(op, Ml_r0, house_dot)
         V = hh.V
     invariant = False
     steps = 0

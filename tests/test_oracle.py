@@ -115,6 +115,24 @@ def test_oracle_minres_histories(golden):
     _check("cg_w20spd_weighted", *K.cg(Ws.astype(np.float64), np.ones(Ws.shape[0]), inner=inner_s, tol=1e-8), d)
 
 
+@pytest.mark.parametrize("cid", __import__("tests.f32_cases", fromlist=["PINNED"]).PINNED)
+def test_oracle_float32_default_inner(cid):
+    """Unweighted float32: the oracle's cg / gmres / minres are bitwise the
+    reference's own runs (tests/golden/f32.npz, make_f32.py) in history and
+    xk, with its dtypes (float32; MINRES keeps its history in float64), at
+    every n mod 4, for k = 1, 2 and 3 and the three orthogonalisations."""
+    from tests import f32_cases as F
+
+    d = np.load(os.path.join(HERE, "golden", "f32.npz"))
+    run = F.run_oracle(F.case(cid), np.float32)
+    assert run["numsteps"] == int(d[cid + "_numsteps"]) and run["success"] == bool(d[cid + "_success"])
+    for key in ("resnorms", "xk"):
+        want = d[f"{cid}_{key}"]
+        assert run[key].dtype == want.dtype == np.dtype(str(d[f"{cid}_{key}_dtype"]))
+        assert run[key].shape == want.shape
+        np.testing.assert_array_equal(run[key].view(np.uint8), want.view(np.uint8))
+
+
 def test_oracle_givens(golden):
     d = golden["lartg"]
     G, r = K.givens(d["fg"].T.copy())
