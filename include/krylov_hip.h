@@ -187,6 +187,18 @@ int kry_dia_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices
  * values[slots / 128] in `dtype` (0 where not flagged). */
 int kry_dia_uniform_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data, int dtype,
                          int itype, int64_t *info, int32_t *flags, void *values);
+/* Host-only view of the diagonal-offset image's descriptor classes (no device
+ * needed, kry_version() >= 112). A slice's descriptor block is its width and,
+ * per slot column, the offset, both lane masks, the uniform flag and the bit
+ * pattern of the uniform value; slices whose blocks are byte-equal share one
+ * class (numbered by first occurrence), and the single-RHS kernel reads the
+ * class's descriptors from a table of the distinct blocks. The image takes
+ * classes only when that table is smaller than the per-slice descriptors and
+ * at most 1 MiB. `uniform` = 0 builds the image without uniform slot columns
+ * (KRY_DIA_UNIFORM=0). info[0..3] = built (0/1), slot columns, classes,
+ * class-table columns (both 0 when the image takes no classes). */
+int kry_dia_class_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data, int dtype,
+                       int itype, int uniform, int64_t *info);
 /* Host-only view of the paired-row SELL-128 plan (no device needed; the
  * image kry_csr_create builds for a general matrix, kry_version() >= 102):
  * info[0..3] = built (0 = refused: a slot column spans more than 65534
@@ -236,7 +248,13 @@ int kry_cb_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices,
  * descriptor (the default while (n + 2) * 8 bytes fit it), 0 when it forms
  * per-lane 64-bit addresses (KRY_DIA_LEAN=0, or a larger n) or there is no
  * such image. */
-#define KRY_CSR_INFO_LEN 16
+/* then (kry_version() >= 112) dia_classes and dia_class_cols: the descriptor
+ * classes the single-RHS kernel of the diagonal-offset image reads (see
+ * kry_dia_class_plan) and the slot columns of their table; both 0 when the
+ * image took none, with KRY_DIA_CLASSES=0, or when the table exceeds
+ * KRY_DIA_CLASS_MAX_BYTES (read at the operator's first use; it can only
+ * lower the 1 MiB limit). */
+#define KRY_CSR_INFO_LEN 18
 int kry_csr_info_n(const kry_csr *A, int64_t *info, int32_t len);
 /* The version-100 form: info[0..4] only (`info` holds 5 values). */
 int kry_csr_info(const kry_csr *A, int64_t *info);

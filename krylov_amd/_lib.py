@@ -77,6 +77,7 @@ _SIGNATURES = {
     "kry_csr_layout": [_i64, _vp, _int, _ip64, _ip64, _ip64],
     "kry_dia_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp, _vp, _vp],
     "kry_dia_uniform_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _int, _int, _ip64, _vp, _vp],
+    "kry_dia_class_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _int, _int, _int, _ip64],
     "kry_pair_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp, _vp, _vp],
     "kry_cb_plan": [ctypes.c_int64, ctypes.c_int64, _vp, _vp, _int, _ip64, _vp],
     "kry_csr_info": [_vp, _ip64],
@@ -305,6 +306,24 @@ def dia_uniform_plan(indptr, indices, data):
     values = np.zeros(int(info[1]), dtype=data.dtype)
     check(lib.kry_dia_uniform_plan(*args, ptr(flags), ptr(values)))
     return {"cols": int(info[1]), "uniform": int(info[2]), "flags": flags, "values": values}
+
+
+def dia_class_plan(indptr, indices, data, uniform=True):
+    """Host-only view of the diagonal-offset image's descriptor classes
+    (kry_dia_class_plan): None if the image would not be built, else
+    {"cols", "classes", "class_cols"} (the last two 0 without classes)."""
+    indptr = np.ascontiguousarray(indptr)
+    indices = np.ascontiguousarray(indices, dtype=indptr.dtype)
+    data = np.ascontiguousarray(data)
+    n, nnz = indptr.shape[0] - 1, indices.shape[0]
+    assert data.shape[0] == nnz
+    info = np.zeros(4, dtype=np.int64)
+    check(lib.kry_dia_class_plan(n, nnz, ptr(indptr), ptr(indices), ptr(data), dtype_code(data.dtype),
+                                 itype_code(indptr.dtype), 1 if uniform else 0,
+                                 info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+    if not info[0]:
+        return None
+    return {"cols": int(info[1]), "classes": int(info[2]), "class_cols": int(info[3])}
 
 
 def pair_plan(indptr, indices):

@@ -431,7 +431,9 @@ extern "C" {
 // kry_gmres_xk_device. 107: uniform slot columns of the diagonal-offset image
 // (kry_csr_info_n: two more values; kry_dia_uniform_plan; kry_csr_compare:
 // bits 23-25). 111: kry_csr_info_n reports the lean diagonal-offset kernel.
-int kry_version(void) { return 111; }
+// 112: descriptor classes of the diagonal-offset image (kry_csr_info_n: two
+// more values; kry_dia_class_plan; kry_csr_compare: bits 26-32).
+int kry_version(void) { return 112; }
 
 #ifndef KRY_BUILD_ID
 #define KRY_BUILD_ID "unknown"
@@ -516,7 +518,9 @@ int kry_csr_info_n(const kry_csr *A, int64_t *info, int32_t len) {
                                          A->dia ? (A->dia_nslots / kDiaSlice - A->dia_nuniform) * kDiaSlice *
                                                       (int64_t)dsize(A->dtype)
                                                 : 0,
-                                         A->dia && dia_lean_on(A) ? 1 : 0};
+                                         A->dia && dia_lean_on(A) ? 1 : 0,
+                                         dia_classes_on(A) ? A->dia_ncls : 0,
+                                         dia_classes_on(A) ? A->dia_cls_cols : 0};
   for (int i = 0; i < len && i < KRY_CSR_INFO_LEN; ++i) info[i] = all[i];
   KRY_API_END
 }
@@ -693,6 +697,22 @@ void csr_upload(kry_csr *A, const I *ip, const I *ix, const MV *dv, const std::v
       KRY_HIP(hipMemcpyAsync(A->dia_val, dh.val.data(), dh.val.size() * sizeof(MV), hipMemcpyHostToDevice, st));
       KRY_HIP(hipMemcpyAsync(A->dia_uflag, dh.uflag.data(), dh.uflag.size() * 4, hipMemcpyHostToDevice, st));
       KRY_HIP(hipMemcpyAsync(A->dia_uval, dh.uval.data(), dh.uval.size() * sizeof(MV), hipMemcpyHostToDevice, st));
+      DiaClassHost<MV> ch;
+      if (dia_classes(dh, ch)) {
+        A->dia_ncls = ch.nclasses;
+        A->dia_cls_cols = ch.ncols;
+        A->dia_cls_word = dev_alloc(ch.word.size() * 4 + 16);  // one word past the last slice: read ahead
+        A->dia_cls_off = dev_alloc(ch.off.size() * 4);
+        A->dia_cls_mask = dev_alloc(ch.mask.size() * 8);
+        A->dia_cls_uflag = dev_alloc(ch.uflag.size() * 4);
+        A->dia_cls_uval = dev_alloc(ch.uval.size() * sizeof(MV));
+        KRY_HIP(hipMemsetAsync(static_cast<char *>(A->dia_cls_word) + ch.word.size() * 4, 0, 16, st));
+        KRY_HIP(hipMemcpyAsync(A->dia_cls_word, ch.word.data(), ch.word.size() * 4, hipMemcpyHostToDevice, st));
+        KRY_HIP(hipMemcpyAsync(A->dia_cls_off, ch.off.data(), ch.off.size() * 4, hipMemcpyHostToDevice, st));
+        KRY_HIP(hipMemcpyAsync(A->dia_cls_mask, ch.mask.data(), ch.mask.size() * 8, hipMemcpyHostToDevice, st));
+        KRY_HIP(hipMemcpyAsync(A->dia_cls_uflag, ch.uflag.data(), ch.uflag.size() * 4, hipMemcpyHostToDevice, st));
+        KRY_HIP(hipMemcpyAsync(A->dia_cls_uval, ch.uval.data(), ch.uval.size() * sizeof(MV), hipMemcpyHostToDevice, st));
+      }
       KRY_HIP(hipStreamSynchronize(st));
       release_later(dh.val);
     }
@@ -793,7 +813,8 @@ static void csr_free(kry_csr *A) {
                   A->cb_val, A->dia_sptr, A->dia_width, A->dia_off, A->dia_mask, A->dia_val,
                   A->sp_sptr, A->sp_width, A->sp_cbase, A->sp_delta, A->sp_val,
                   A->rs_sptr, A->rs_width, A->rs_colrank, A->rs_val, A->perm, A->iperm,
-                  A->dia_uflag, A->dia_uval};
+                  A->dia_uflag, A->dia_uval, A->dia_cls_word, A->dia_cls_off, A->dia_cls_mask,
+                  A->dia_cls_uflag, A->dia_cls_uval};
   for (void *b : bufs) dev_free(b);
 }
 
@@ -918,6 +939,25 @@ int kry_csr_compare(const kry_csr *A, const kry_csr *B, int64_t *out) {
     note(A->dia_nuniform != B->dia_nuniform);
     buf(A->dia_uflag, B->dia_uflag, A->dia ? dc * 4 : 0);
     buf(A->dia_uval, B->dia_uval, A->dia ? dc * ds : 0);
+    // the descriptor classes (bits 26 to 32): their count, the table's columns,
+    // the class words, the table. The classes are a function of the
+    // descriptors above: compared only where those are equal (two images
+    // that differ there already, as with uniform detection on and off, say
+    // nothing more by differing here)
+    const bool same_desc = nd == 0;
+    if (same_desc) {
+      note(A->dia_ncls != B->dia_ncls);
+      note(A->dia_cls_cols != B->dia_cls_cols);
+    }
+    if (same_desc && A->dia_ncls == B->dia_ncls && A->dia_cls_cols == B->dia_cls_cols) {
+      const int64_t cc = A->dia_cls_cols + kDiaPad;
+      const bool on = A->dia && A->dia_ncls > 0;
+      buf(A->dia_cls_word, B->dia_cls_word, on ? A->dia_nslices * 8 : 0);
+      buf(A->dia_cls_off, B->dia_cls_off, on ? cc * 4 : 0);
+      buf(A->dia_cls_mask, B->dia_cls_mask, on ? cc * 16 : 0);
+      buf(A->dia_cls_uflag, B->dia_cls_uflag, on ? cc * 4 : 0);
+      buf(A->dia_cls_uval, B->dia_cls_uval, on ? cc * ds : 0);
+    }
   }
   out[0] = nd;
   out[1] = mask;

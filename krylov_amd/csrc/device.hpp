@@ -632,9 +632,21 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(
 // no address of its own: per slot column one address add, two products, two
 // adds and the selects. The same loads for present lanes, the same products,
 // adds and selects: the same bits.
+// Descriptor classes (cword != null; launch_spmv: dia_classes_on): a slice's
+// descriptor block depends only on where the grid's boundaries fall inside
+// its rows, so the image keeps the distinct blocks once, in a class table,
+// and per slice a class word (the block's first column in the table, the
+// width). doff, dmask, duflag and duval then are the table (the metric: 839
+// columns, 27 KB, resident in L2 and the scalar cache) instead of the
+// per-slice arrays (1,175,184 columns, 37.6 MB streamed from HBM per launch,
+// at the head of every round's chain), and a round that reads past the
+// block's width reads a later class's columns, dropped like a later slice's.
+// sptr is read only for the streamed values (UNI != 2), swidth not at all.
+// The same descriptor bytes reach the same instructions: the same bits.
 template <typename V, typename MV, int UNR, class Src, class Epi, int UNI = 1, bool LEAN = false>
 __global__ __launch_bounds__(kBlock) void spmv_dia_kernel(const int64_t *__restrict__ sptr,
                                                           const int *__restrict__ swidth,
+                                                          const int2 *__restrict__ cword,
                                                           const int *__restrict__ doff,
                                                           const uint64_t *__restrict__ dmask,
                                                           const int *__restrict__ duflag,
@@ -671,11 +683,25 @@ __global__ __launch_bounds__(kBlock) void spmv_dia_kernel(const int64_t *__restr
       dacc += epi(prow, 0, pend[0], bs(prow, 0));
     }
   };
+  // the class word of the wave's next slice (its slices are contiguous, the
+  // array holds one word past the last slice): loaded a slice ahead, off the
+  // chain word -> descriptors -> x loads
+  int2 cnext = cword ? cword[s_begin] : int2{0, 0};
   for (int64_t s = s_begin; s < s_end; ++s) {
-    const int w = swidth[s];
-    const int64_t base = sptr[s];
+    int w;
+    int64_t c0;
+    [[maybe_unused]] int64_t base = 0;
+    if (cword) {  // descriptor classes: doff, dmask, duflag, duval are the class table
+      c0 = cnext.x;
+      w = cnext.y;
+      cnext = cword[s + 1];
+      if constexpr (UNI != 2) base = sptr[s];
+    } else {
+      w = swidth[s];
+      base = sptr[s];
+      c0 = base / kDiaSlice;
+    }
     const int64_t row = s * kDiaSlice + 2 * lane;
-    const int64_t c0 = base / kDiaSlice;
     const int *mo = doff + c0;  // wave-uniform: scalar loads
     const uint64_t *mk = dmask + 2 * c0;
     const int *mu = duflag + c0;
@@ -1718,6 +1744,24 @@ inline bool dia_lean_on(const kry_csr *A) {
   return A->dia_lean == 1;
 }
 
+// Descriptor classes (kry_csr::dia_cls_*): the k = 1 kernel reads each slice's
+// class word and the class table instead of the per-slice descriptors while
+// the operator has classes. KRY_DIA_CLASSES=0: the per-slice arrays for every
+// operator (A/B and tests); KRY_DIA_CLASS_MAX_BYTES lowers the table's size
+// limit (tests: the fallback on a small image). Both are read at the
+// operator's first use; kry_csr_info_n reports the choice.
+inline bool dia_classes_on(const kry_csr *A) {
+  if (A->dia_cls < 0) {
+    const char *e = getenv("KRY_DIA_CLASSES"), *m = getenv("KRY_DIA_CLASS_MAX_BYTES");
+    const int64_t cap = m ? std::min<int64_t>(kDiaClassMaxBytes, atoll(m)) : kDiaClassMaxBytes;
+    A->dia_cls = A->dia && A->dia_ncls > 0 && !(e && atoi(e) == 0) &&
+                         A->dia_cls_cols * dia_class_col_bytes(dsize(A->dtype)) <= cap
+                     ? 1
+                     : 0;
+  }
+  return A->dia_cls == 1;
+}
+
 template <typename I>
 inline bool spmv_column_blocked(const kry_csr *A, int k) {
   return sizeof(I) == 4 && k == 1 && !A->dia && A->cb_nb > 0;
@@ -1796,12 +1840,16 @@ void launch_spmv(const kry_csr *A, int k, Src src, Epi epi, double *part, int *g
                           : allu                             ? kDiaGridUniform
                                                              : kMaxGridBlk;
       grid = (int)std::max<int64_t>(1, std::min<int64_t>(dia_cap, (A->dia_nslices + 3) / 4));
+      const bool cls = dia_classes_on(A);
       auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, static_cast<const int64_t *>(A->dia_sptr),
-                           static_cast<const int *>(A->dia_width), static_cast<const int *>(A->dia_off),
-                           static_cast<const uint64_t *>(A->dia_mask), static_cast<const int *>(A->dia_uflag),
-                           static_cast<const MV *>(A->dia_uval), static_cast<const MV *>(A->dia_val),
-                           A->dia_nslices, A->n, src, epi, part, ctrl, step);
+                           static_cast<const int *>(A->dia_width),
+                           static_cast<const int2 *>(cls ? A->dia_cls_word : nullptr),
+                           static_cast<const int *>(cls ? A->dia_cls_off : A->dia_off),
+                           static_cast<const uint64_t *>(cls ? A->dia_cls_mask : A->dia_mask),
+                           static_cast<const int *>(cls ? A->dia_cls_uflag : A->dia_uflag),
+                           static_cast<const MV *>(cls ? A->dia_cls_uval : A->dia_uval),
+                           static_cast<const MV *>(A->dia_val), A->dia_nslices, A->n, src, epi, part, ctrl, step);
       };
       // all uniform: 8 slot columns per round also for wide images (16 per
       // round: 104 VGPRs, 4 waves per SIMD, metric CG 0.200 against 0.180 ms

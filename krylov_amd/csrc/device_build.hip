@@ -21,9 +21,16 @@
 //                      binary search, its lane-mask bit (LDS atomicOr), its
 //                      value; then per slot column whether its present rows
 //                      all store one bit pattern (dia_build's uniform flag)
+//   dia_class_*_kernel the descriptor classes (dia_classes): a hash per
+//                      slice's block, grouped on the host from one small D2H
+//                      copy; the table gathered from each group's first
+//                      slice; every slice verified against it byte for byte
 // Slot pointers are exclusive scans of the per-slice slot counts
 // (hipcub::DeviceScan). Vector atomics only.
 #include <hipcub/hipcub.hpp>
+
+#include <unordered_map>
+#include <vector>
 
 #include "common.hpp"
 #include "host_image.hpp"
@@ -276,6 +283,79 @@ __global__ __launch_bounds__(kDb) void dia_fill_kernel(int64_t n, const int32_t 
   if (lane == 0 && nu) atomicAdd(nuniform, (unsigned long long)nu);
 }
 
+// Descriptor classes (dia_classes): a 64-bit hash of every slice's descriptor
+// block, one thread per slice. The hash only groups; dia_class_verify_kernel
+// decides equality on the bytes.
+template <typename MV>
+__device__ inline uint64_t uval_bits(MV v) {
+  if constexpr (sizeof(MV) == 8) return (uint64_t)__double_as_longlong(v);
+  else return (uint64_t)__float_as_uint(v);
+}
+__device__ inline uint64_t hash_mix(uint64_t h, uint64_t v) {
+  h = (h ^ v) * 0x9E3779B97F4A7C15ull;
+  return h ^ (h >> 29);
+}
+template <typename MV>
+__global__ __launch_bounds__(kDb) void dia_class_hash_kernel(int64_t ns, const long long *__restrict__ sptr,
+                                                             const int *__restrict__ width,
+                                                             const int32_t *__restrict__ off,
+                                                             const uint64_t *__restrict__ mask,
+                                                             const int32_t *__restrict__ uflag,
+                                                             const MV *__restrict__ uval, uint64_t *__restrict__ hash) {
+  const int64_t s = (int64_t)blockIdx.x * kDb + threadIdx.x;
+  if (s >= ns) return;
+  const int64_t c0 = sptr[s] / kDiaSlice;
+  const int w = width[s];
+  uint64_t h = hash_mix(0x2545F4914F6CDD1Dull, (uint64_t)w);
+  for (int64_t j = c0; j < c0 + w; ++j) {
+    h = hash_mix(h, (uint32_t)off[j] | (uint64_t)(uint32_t)uflag[j] << 32);
+    h = hash_mix(h, mask[2 * j]);
+    h = hash_mix(h, mask[2 * j + 1]);
+    h = hash_mix(h, uval_bits(uval[j]));
+  }
+  hash[s] = h;
+}
+
+// The class table: class k's block copied from its first slice's columns
+// (rep_c0[k] ...) to the table's columns first[k] ..., one thread per class.
+template <typename MV>
+__global__ __launch_bounds__(kDb) void dia_class_gather_kernel(
+    int64_t ncls, const long long *__restrict__ rep_c0, const int32_t *__restrict__ first,
+    const int32_t *__restrict__ cwidth, const int32_t *__restrict__ off, const uint64_t *__restrict__ mask,
+    const int32_t *__restrict__ uflag, const MV *__restrict__ uval, int32_t *__restrict__ toff,
+    uint64_t *__restrict__ tmask, int32_t *__restrict__ tuflag, MV *__restrict__ tuval) {
+  const int64_t k = (int64_t)blockIdx.x * kDb + threadIdx.x;
+  if (k >= ncls) return;
+  const int64_t c0 = rep_c0[k], t0 = first[k];
+  for (int j = 0; j < cwidth[k]; ++j) {
+    toff[t0 + j] = off[c0 + j];
+    tmask[2 * (t0 + j)] = mask[2 * (c0 + j)];
+    tmask[2 * (t0 + j) + 1] = mask[2 * (c0 + j) + 1];
+    tuflag[t0 + j] = uflag[c0 + j];
+    tuval[t0 + j] = uval[c0 + j];
+  }
+}
+
+// Every slice's block against its class's block in the table, byte for byte
+// (one thread per slice); any difference sets *bad.
+template <typename MV>
+__global__ __launch_bounds__(kDb) void dia_class_verify_kernel(
+    int64_t ns, const long long *__restrict__ sptr, const int *__restrict__ width, const int32_t *__restrict__ word,
+    const int32_t *__restrict__ off, const uint64_t *__restrict__ mask, const int32_t *__restrict__ uflag,
+    const MV *__restrict__ uval, const int32_t *__restrict__ toff, const uint64_t *__restrict__ tmask,
+    const int32_t *__restrict__ tuflag, const MV *__restrict__ tuval, unsigned *bad) {
+  const int64_t s = (int64_t)blockIdx.x * kDb + threadIdx.x;
+  if (s >= ns) return;
+  const int64_t c0 = sptr[s] / kDiaSlice, t0 = word[2 * s];
+  const int w = width[s];
+  bool ok = word[2 * s + 1] == w;
+  for (int j = 0; j < w && ok; ++j)
+    ok = off[c0 + j] == toff[t0 + j] && mask[2 * (c0 + j)] == tmask[2 * (t0 + j)] &&
+         mask[2 * (c0 + j) + 1] == tmask[2 * (t0 + j) + 1] && uflag[c0 + j] == tuflag[t0 + j] &&
+         uval_bits(uval[c0 + j]) == uval_bits(tuval[t0 + j]);
+  if (!ok) atomicOr(bad, 1u);
+}
+
 int grid_for_n(int64_t items, int per_block) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, (items + per_block - 1) / per_block));
 }
@@ -317,6 +397,82 @@ T read1(const T *d, hipStream_t st) {
   KRY_HIP(hipMemcpyAsync(&v, d, sizeof(T), hipMemcpyDeviceToHost, st));
   KRY_HIP(hipStreamSynchronize(st));
   return v;
+}
+
+// The descriptor classes of the image just built (A->dia_*), byte-equal to
+// dia_classes': the slices are grouped by their blocks' hashes on the host
+// (one D2H copy of 20 bytes per slice), each group's first slice is its
+// representative, the table is gathered from the representatives, and every
+// slice is then verified against its class in the table byte for byte. A
+// mismatch (two different blocks with one hash) records no classes.
+template <typename MV>
+void device_dia_classes(kry_csr *A, hipStream_t st) {
+  const int64_t ns = A->dia_nslices, cols = A->dia_nslots / kDiaSlice;
+  if (ns == 0) return;
+  const auto *sptr = static_cast<const long long *>(A->dia_sptr);
+  const auto *width = static_cast<const int *>(A->dia_width);
+  const auto *off = static_cast<const int32_t *>(A->dia_off);
+  const auto *mask = static_cast<const uint64_t *>(A->dia_mask);
+  const auto *uflag = static_cast<const int32_t *>(A->dia_uflag);
+  const auto *uval = static_cast<const MV *>(A->dia_uval);
+  Tmp dhash((size_t)ns * 8);
+  hipLaunchKernelGGL(dia_class_hash_kernel<MV>, dim3(grid_for_n(ns, kDb)), dim3(kDb), 0, st, ns, sptr, width, off, mask,
+                     uflag, uval, dhash.as<uint64_t>());
+  KRY_HIP(hipGetLastError());
+  std::vector<uint64_t> hash(ns);
+  std::vector<long long> hsptr(ns + 1);
+  std::vector<int32_t> hwidth(ns);
+  KRY_HIP(hipMemcpyAsync(hash.data(), dhash.p, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
+  KRY_HIP(hipMemcpyAsync(hsptr.data(), sptr, (size_t)(ns + 1) * 8, hipMemcpyDeviceToHost, st));
+  KRY_HIP(hipMemcpyAsync(hwidth.data(), width, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
+  KRY_HIP(hipStreamSynchronize(st));
+  const int64_t col_bytes = dia_class_col_bytes(sizeof(MV));
+  std::unordered_map<uint64_t, int32_t> cls_of;  // hash -> class
+  std::vector<long long> rep_c0;
+  std::vector<int32_t> first, cwidth, word(2 * ns);
+  int64_t ccols = 0;
+  for (int64_t s = 0; s < ns; ++s) {
+    auto it = cls_of.find(hash[s]);
+    if (it == cls_of.end()) {
+      it = cls_of.emplace(hash[s], (int32_t)rep_c0.size()).first;
+      rep_c0.push_back(hsptr[s] / kDiaSlice);
+      first.push_back((int32_t)ccols);
+      cwidth.push_back(hwidth[s]);
+      ccols += hwidth[s];
+      // as dia_classes refuses: not smaller than the per-slice descriptors, or past the L2 share
+      if (ccols >= cols || ccols * col_bytes > kDiaClassMaxBytes) return;
+    }
+    word[2 * s] = first[it->second];
+    word[2 * s + 1] = cwidth[it->second];
+  }
+  const int64_t ncls = (int64_t)rep_c0.size(), tc = ccols + kDiaPad;
+  Tmp dword((size_t)ns * 8 + 16), toff((size_t)tc * 4), tmask((size_t)tc * 16), tuflag((size_t)tc * 4),
+      tuval((size_t)tc * sizeof(MV)), drep((size_t)ncls * 8), dfirst((size_t)ncls * 4), dcw((size_t)ncls * 4), dbad(16);
+  KRY_HIP(hipMemsetAsync(static_cast<char *>(dword.p) + (size_t)ns * 8, 0, 16, st));  // one word past the last slice
+  KRY_HIP(hipMemsetAsync(toff.p, 0, (size_t)tc * 4, st));
+  KRY_HIP(hipMemsetAsync(tmask.p, 0, (size_t)tc * 16, st));
+  KRY_HIP(hipMemsetAsync(tuflag.p, 0, (size_t)tc * 4, st));
+  KRY_HIP(hipMemsetAsync(tuval.p, 0, (size_t)tc * sizeof(MV), st));
+  KRY_HIP(hipMemsetAsync(dbad.p, 0, 16, st));
+  KRY_HIP(hipMemcpyAsync(dword.p, word.data(), (size_t)ns * 8, hipMemcpyHostToDevice, st));
+  KRY_HIP(hipMemcpyAsync(drep.p, rep_c0.data(), (size_t)ncls * 8, hipMemcpyHostToDevice, st));
+  KRY_HIP(hipMemcpyAsync(dfirst.p, first.data(), (size_t)ncls * 4, hipMemcpyHostToDevice, st));
+  KRY_HIP(hipMemcpyAsync(dcw.p, cwidth.data(), (size_t)ncls * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(dia_class_gather_kernel<MV>, dim3(grid_for_n(ncls, kDb)), dim3(kDb), 0, st, ncls,
+                     drep.as<const long long>(), dfirst.as<const int32_t>(), dcw.as<const int32_t>(), off, mask, uflag,
+                     uval, toff.as<int32_t>(), tmask.as<uint64_t>(), tuflag.as<int32_t>(), tuval.as<MV>());
+  hipLaunchKernelGGL(dia_class_verify_kernel<MV>, dim3(grid_for_n(ns, kDb)), dim3(kDb), 0, st, ns, sptr, width,
+                     dword.as<const int32_t>(), off, mask, uflag, uval, toff.as<const int32_t>(),
+                     tmask.as<const uint64_t>(), tuflag.as<const int32_t>(), tuval.as<const MV>(), dbad.as<unsigned>());
+  KRY_HIP(hipGetLastError());
+  if (read1(dbad.as<const unsigned>(), st) != 0) return;  // (the sync also keeps the host vectors alive long enough)
+  A->dia_ncls = ncls;
+  A->dia_cls_cols = ccols;
+  A->dia_cls_word = dword.release();
+  A->dia_cls_off = toff.release();
+  A->dia_cls_mask = tmask.release();
+  A->dia_cls_uflag = tuflag.release();
+  A->dia_cls_uval = tuval.release();
 }
 
 }  // namespace
@@ -440,6 +596,7 @@ int device_image_build(kry_csr *A, const int32_t *ip, const int32_t *ix, const M
         A->dia_val = dval.release();
         A->dia_uflag = duflag.release();
         A->dia_uval = duval.release();
+        device_dia_classes<MV>(A, st);
       }
     }
   }

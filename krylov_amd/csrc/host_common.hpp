@@ -19,6 +19,11 @@ constexpr int kSlice = 64;           // SELL slice height = one wavefront
 // of the wave owns rows 2l and 2l + 1 of its slice
 constexpr int kDiaSlice = 128;
 constexpr int kDiaPad = 32;  // slot-column descriptors past the last one (unconditional reads of a round)
+// descriptor classes (kry_csr::dia_cls_*): the class table may take a quarter
+// of one XCD's 4 MiB L2; a column of it holds an int32 offset, two uint64
+// masks, an int32 flag and a value
+constexpr int64_t kDiaClassMaxBytes = int64_t(1) << 20;
+constexpr int64_t dia_class_col_bytes(size_t value_size) { return 4 + 16 + 4 + (int64_t)value_size; }
 // paired-row SELL-128 image (kry_csr::sp_*): lane l owns rows 2l, 2l + 1
 constexpr int kPairSlice = 128;
 constexpr int kCbRows = 256;         // rows per column-blocked segment (one per thread)

@@ -12,6 +12,7 @@
 #include <functional>
 #include <thread>
 #include <type_traits>
+#include <unordered_map>
 
 namespace kry {
 
@@ -306,6 +307,95 @@ bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_s
     for (auto &x : th) x.join();
   }
   d.nuniform = nuniform.load();
+  return true;
+}
+
+// Descriptor classes (DiaClassHost): an exact map over the block bytes. A
+// 64-bit hash per slice (threaded) only picks the bucket; within a bucket a
+// block is compared field by field with every class already there, so two
+// slices share a class exactly when their blocks are byte-equal.
+template <typename MV>
+bool dia_classes(const DiaHost<MV> &d, DiaClassHost<MV> &c) {
+  c = DiaClassHost<MV>();
+  const int64_t ns = (int64_t)d.width.size();
+  if (ns == 0) return false;
+  const int64_t cols = d.sptr[ns] / kDiaSlice;
+  std::vector<uint64_t> hash(ns);
+  auto mix = [](uint64_t h, uint64_t v) {
+    h = (h ^ v) * 0x9E3779B97F4A7C15ull;
+    return h ^ (h >> 29);
+  };
+  auto hpass = [&](int64_t sa, int64_t sb) {
+    for (int64_t s = sa; s < sb; ++s) {
+      const int64_t c0 = d.sptr[s] / kDiaSlice;
+      uint64_t h = mix(0x2545F4914F6CDD1Dull, (uint64_t)d.width[s]);
+      for (int64_t j = c0; j < c0 + d.width[s]; ++j) {
+        h = mix(h, (uint32_t)d.off[j] | (uint64_t)(uint32_t)d.uflag[j] << 32);
+        h = mix(h, d.mask[2 * j]);
+        h = mix(h, d.mask[2 * j + 1]);
+        h = mix(h, value_bits(d.uval[j]));
+      }
+      hash[s] = h;
+    }
+  };
+  {
+    unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    if (ns < 2048) nt = 1;
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; ++t) th.emplace_back(hpass, ns * t / nt, ns * (t + 1) / nt);
+    for (auto &x : th) x.join();
+  }
+  auto same = [&](int64_t a, int64_t b) {  // slices a and b: byte-equal blocks
+    const int w = d.width[a];
+    if (w != d.width[b]) return false;
+    const int64_t ca = d.sptr[a] / kDiaSlice, cb = d.sptr[b] / kDiaSlice;
+    return std::memcmp(&d.off[ca], &d.off[cb], (size_t)w * 4) == 0 &&
+           std::memcmp(&d.mask[2 * ca], &d.mask[2 * cb], (size_t)w * 16) == 0 &&
+           std::memcmp(&d.uflag[ca], &d.uflag[cb], (size_t)w * 4) == 0 &&
+           std::memcmp(&d.uval[ca], &d.uval[cb], (size_t)w * sizeof(MV)) == 0;
+  };
+  const int64_t col_bytes = dia_class_col_bytes(sizeof(MV));
+  std::unordered_multimap<uint64_t, int32_t> bucket;  // hash -> class
+  std::vector<int64_t> rep;                           // class -> its first slice
+  std::vector<int32_t> first;                         // class -> its first column in the table
+  std::vector<int32_t> cls(ns);
+  int64_t ccols = 0;
+  for (int64_t s = 0; s < ns; ++s) {
+    int32_t k = -1;
+    auto range = bucket.equal_range(hash[s]);
+    for (auto it = range.first; it != range.second && k < 0; ++it)
+      if (same(rep[it->second], s)) k = it->second;
+    if (k < 0) {
+      k = (int32_t)rep.size();
+      rep.push_back(s);
+      first.push_back((int32_t)ccols);
+      bucket.emplace(hash[s], k);
+      ccols += d.width[s];
+      // not smaller than the per-slice descriptors, or past the L2 share: no classes
+      if (ccols >= cols || ccols * col_bytes > kDiaClassMaxBytes) return false;
+    }
+    cls[s] = k;
+  }
+  if (ccols >= cols) return false;
+  c.nclasses = (int64_t)rep.size();
+  c.ncols = ccols;
+  c.word.resize(2 * ns);
+  for (int64_t s = 0; s < ns; ++s) {
+    c.word[2 * s] = first[cls[s]];
+    c.word[2 * s + 1] = d.width[s];
+  }
+  c.off.assign(ccols + kDiaPad, 0);
+  c.mask.assign(2 * (ccols + kDiaPad), 0);
+  c.uflag.assign(ccols + kDiaPad, 0);
+  c.uval.assign(ccols + kDiaPad, MV(0));
+  for (size_t k = 0; k < rep.size(); ++k) {
+    const int64_t c0 = d.sptr[rep[k]] / kDiaSlice;
+    const int w = d.width[rep[k]];
+    std::copy_n(&d.off[c0], w, &c.off[first[k]]);
+    std::copy_n(&d.mask[2 * c0], 2 * w, &c.mask[2 * (int64_t)first[k]]);
+    std::copy_n(&d.uflag[c0], w, &c.uflag[first[k]]);
+    std::copy_n(&d.uval[c0], w, &c.uval[first[k]]);
+  }
   return true;
 }
 
@@ -654,6 +744,25 @@ static void dia_uniform_plan_host(int64_t n, int64_t nnz, const I *ip, const I *
   if (!built) return;
   if (flags) std::copy(d.uflag.begin(), d.uflag.begin() + cols, flags);
   if (values) std::memcpy(values, d.uval.data(), (size_t)cols * sizeof(MV));
+}
+
+// Host-only view of the descriptor classes dia_classes finds
+// (kry_dia_class_plan): info = {built, slot columns, classes, class-table
+// columns}; the last two are 0 when the image takes no classes.
+template <typename I, typename MV>
+static void dia_class_plan_host(int64_t n, int64_t nnz, const I *ip, const I *ix, const MV *dv, int uniform,
+                                int64_t *info) {
+  check_csr(n, nnz, ip, ix);
+  int64_t ns = 0, sell_slots = 0, irr = 0;
+  sell_plan(n, ip, nullptr, nullptr, &ns, &sell_slots, &irr);
+  DiaHost<MV> d;
+  const bool built = dia_build(n, ip, ix, dv, sell_slots, d, uniform != 0);
+  DiaClassHost<MV> c;
+  const bool cls = built && dia_classes(d, c);
+  info[0] = built ? 1 : 0;
+  info[1] = built ? d.sptr.back() / kDiaSlice : 0;
+  info[2] = cls ? c.nclasses : 0;
+  info[3] = cls ? c.ncols : 0;
 }
 
 // Column-blocked image (see kry_csr::cb_*). Returns false when not useful or
@@ -1096,6 +1205,8 @@ KRY_HOST_IM(int32_t, float)
 KRY_HOST_IM(int32_t, double)
 KRY_HOST_IM(int64_t, float)
 KRY_HOST_IM(int64_t, double)
+template bool dia_classes<float>(const DiaHost<float> &, DiaClassHost<float> &);
+template bool dia_classes<double>(const DiaHost<double> &, DiaClassHost<double> &);
 template void release_later<int32_t>(hvec<int32_t> &);
 template void release_later<int64_t>(hvec<int64_t> &);
 template void release_later<float>(hvec<float> &);
@@ -1173,6 +1284,26 @@ int kry_dia_uniform_plan(int64_t n, int64_t nnz, const void *indptr, const void 
       dia_uniform_plan_host(n, nnz, ip, ix, static_cast<const double *>(dv), info, flags, static_cast<double *>(values));
     else
       dia_uniform_plan_host(n, nnz, ip, ix, static_cast<const float *>(dv), info, flags, static_cast<float *>(values));
+  };
+  if (itype == KRY_I32)
+    go(static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices));
+  else
+    go(static_cast<const int64_t *>(indptr), static_cast<const int64_t *>(indices));
+  KRY_API_END
+}
+
+int kry_dia_class_plan(int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data, int dtype,
+                       int itype, int uniform, int64_t *info) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(indptr && info && n >= 0 && nnz >= 0 && (nnz == 0 || (indices && data)), KRY_EINVAL,
+              "bad plan arguments");
+  KRY_REQUIRE(dtype == KRY_F32 || dtype == KRY_F64, KRY_EINVAL, "dtype must be f32 or f64");
+  KRY_REQUIRE(itype == KRY_I32 || itype == KRY_I64, KRY_EINVAL, "bad itype");
+  static const double zd = 0;
+  const void *dv = nnz ? data : (const void *)&zd;
+  auto go = [&](auto *ip, auto *ix) {
+    if (dtype == KRY_F64) dia_class_plan_host(n, nnz, ip, ix, static_cast<const double *>(dv), uniform, info);
+    else dia_class_plan_host(n, nnz, ip, ix, static_cast<const float *>(dv), uniform, info);
   };
   if (itype == KRY_I32)
     go(static_cast<const int32_t *>(indptr), static_cast<const int32_t *>(indices));

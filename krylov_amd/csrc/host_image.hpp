@@ -85,6 +85,28 @@ template <typename I, typename MV>
 bool dia_build(int64_t n, const I *ip, const I *ix, const MV *dv, int64_t sell_slots, DiaHost<MV> &d,
                bool uniform = true);
 
+// Descriptor classes of a diagonal-offset image (kry_csr::dia_cls_*). A
+// slice's descriptor block is its width and, per slot column, the offset, both
+// masks, the uniform flag and the bit pattern of the uniform value; slices
+// whose blocks are byte-equal form one class, numbered by first occurrence in
+// slice order. word[2 s], word[2 s + 1] = the first column of slice s's class
+// in the class table, and its width; off / mask / uflag / uval = the distinct
+// blocks concatenated in class order, padded by kDiaPad columns like the
+// per-slice arrays. dia_classes fills `c` and returns true when the table is
+// smaller than the per-slice descriptors and within kDiaClassMaxBytes
+// (dia_class_col_bytes per column); otherwise `c` is left empty: no classes.
+template <typename MV>
+struct DiaClassHost {
+  int64_t nclasses = 0, ncols = 0;
+  std::vector<int32_t> word;
+  std::vector<int32_t> off;
+  std::vector<uint64_t> mask;
+  std::vector<int32_t> uflag;
+  std::vector<MV> uval;
+};
+template <typename MV>
+bool dia_classes(const DiaHost<MV> &d, DiaClassHost<MV> &c);
+
 template <typename MV>
 struct CbHost {
   int64_t nb = 0, cols = 0, ng = 0;

@@ -93,6 +93,27 @@ struct kry_csr {
   // (the lean kernel), 0 = per-lane 64-bit addresses; -1 = not chosen yet
   // (device.hpp dia_lean_on, at the operator's first use)
   mutable int dia_lean = -1;
+  // descriptor classes: a slice's descriptor block (its width and, per slot
+  // column, offset, masks, flag, value bits) depends only on where the grid's
+  // boundaries fall inside its rows, so almost all blocks of a stencil are
+  // copies of a few. Slices with byte-equal blocks share one class (numbered
+  // by first occurrence), and the k = 1 kernel reads the class's columns from
+  // a table of the distinct blocks, which stays in L2 and the scalar cache,
+  // instead of streaming every slice's own copy from HBM. Built only when the
+  // table is smaller than the per-slice descriptors and within
+  // kDiaClassMaxBytes (dia_ncls = 0 otherwise); the per-slice arrays above
+  // stay for the block kernel and the persistent loop.
+  int64_t dia_ncls = 0;           // classes
+  int64_t dia_cls_cols = 0;       // slot columns of the class table
+  void *dia_cls_word = nullptr;   // int32 x 2 per slice (+ pad): the class's first table column, the width
+  void *dia_cls_off = nullptr;    // int32, dia_cls_cols (+ kDiaPad)
+  void *dia_cls_mask = nullptr;   // uint64 x 2 per table column
+  void *dia_cls_uflag = nullptr;  // int32
+  void *dia_cls_uval = nullptr;   // dtype
+  // 1 = the k = 1 kernel reads the class table, 0 = the per-slice arrays
+  // (no classes, KRY_DIA_CLASSES=0, or a table over KRY_DIA_CLASS_MAX_BYTES);
+  // -1 = not chosen yet (device.hpp dia_classes_on, at the operator's first use)
+  mutable int dia_cls = -1;
   // paired-row SELL-128 image (general matrices, k = 1; spmv_pair_kernel):
   // slice s covers rows [128 s, 128 s + 128); slot column j of the slice
   // holds the j-th stored entry of every row, row r at position r - 128 s,

@@ -105,18 +105,23 @@ class CsrOperator:
         """The device image: {"slices", "slots", "irregular", "compact",
         "col_blocks", "dia", "dia_slots", "pair", "pair_slots", "rs",
         "rs_slots", "renumbered", "rcm_levels", "dia_uniform_cols",
-        "dia_value_bytes", "dia_lean"} (kry_csr_info_n). The last three: the
-        slot columns of the diagonal-offset image whose value the single-RHS
-        SpMV reads from its descriptor, the matrix-value bytes it still
-        streams, and whether it loads x through a buffer descriptor (the lean
-        kernel; False with KRY_DIA_LEAN=0 or beyond its size limit)."""
-        info = np.zeros(16, dtype=np.int64)
-        check(lib.kry_csr_info_n(self.handle, info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 16))
+        "dia_value_bytes", "dia_lean", "dia_classes", "dia_class_cols"}
+        (kry_csr_info_n). The last five: the slot columns of the
+        diagonal-offset image whose value the single-RHS SpMV reads from its
+        descriptor, the matrix-value bytes it still streams, whether it loads
+        x through a buffer descriptor (the lean kernel; False with
+        KRY_DIA_LEAN=0 or beyond its size limit), and the descriptor classes
+        it reads (slices with byte-equal descriptor blocks share one) with
+        the slot columns of their table (both 0 without classes:
+        KRY_DIA_CLASSES=0, nothing shared, or a table over the size limit)."""
+        info = np.zeros(18, dtype=np.int64)
+        check(lib.kry_csr_info_n(self.handle, info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 18))
         return {"slices": int(info[0]), "slots": int(info[1]), "irregular": int(info[2]), "compact": bool(info[3]),
                 "col_blocks": int(info[4]), "dia": bool(info[5]), "dia_slots": int(info[6]), "pair": bool(info[7]),
                 "pair_slots": int(info[8]), "rs": bool(info[9]), "rs_slots": int(info[10]),
                 "renumbered": bool(info[11]), "rcm_levels": int(info[12]), "dia_uniform_cols": int(info[13]),
-                "dia_value_bytes": int(info[14]), "dia_lean": bool(info[15])}
+                "dia_value_bytes": int(info[14]), "dia_lean": bool(info[15]),
+                "dia_classes": int(info[16]), "dia_class_cols": int(info[17])}
 
     def matvec_device(self, x, y):
         """y = A x for DeviceVectors in the caller's numbering (no host traffic)."""
