@@ -40,6 +40,7 @@ typedef struct kry_comm kry_comm;
 typedef struct kry_prog kry_prog;
 typedef struct kry_tri kry_tri;
 typedef struct kry_precond kry_precond;
+typedef struct kry_bjacobi kry_bjacobi;
 
 /* value / index types */
 enum { KRY_F32 = 1, KRY_F64 = 2 };
@@ -501,6 +502,67 @@ int kry_prog_precond(kry_prog *p, const kry_precond *P, const kry_vec *x, kry_ve
 int kry_cg_set_precond(kry_cg *s, int32_t slot, const kry_precond *P);
 int kry_gmres_set_precond(kry_gmres *s, int32_t slot, const kry_precond *P);
 int kry_minres_set_precond(kry_minres *s, int32_t slot, const kry_precond *P);
+
+/* ---- block-Jacobi preconditioner (kry_version() >= 113) ----------------------
+ * M = blockdiag(A_11, ..., A_mm)^-1: the diagonal blocks of A inverted once on
+ * the device, an apply one batched dense block product in ONE launch, for up
+ * to 256 columns (a power of two). Partition: starts[nblocks] (int32) with
+ * starts[0] = 0, strictly increasing, every entry < n; block i is rows and
+ * columns [starts[i], starts[i + 1]), n closing the last one; 1 to 32 rows per
+ * block. Block i is the dense b x b array of A's stored entries inside it
+ * (CSR with int32 indices and strictly sorted rows), zeros elsewhere.
+ * Inverse: in-place Gauss-Jordan with row pivoting in `dtype` scalars,
+ *   for c = 0 .. b-1:
+ *     p = c; for r = c+1 .. b-1: if |M[r,c]| > |M[p,c]|: p = r
+ *     swap rows c and p; piv[c] = p
+ *     d = M[c,c]; d == 0 or not finite: the block is singular
+ *     M[c,c] = 1; M[c,j] = M[c,j] / d for every j
+ *     for every r != c: f = M[r,c]; M[r,c] = 0; M[r,j] = M[r,j] - (f * M[c,j]) for every j
+ *   for c = b-1 .. 0: swap columns c and piv[c]
+ * with true divisions and the product rounded before the subtraction (no
+ * FMA): bitwise that sequential loop.
+ * Apply: y[r,c] = sum_j (X[r-s,j] * x[s+j,c]) for row r of a block with rows
+ * [s, s+b) and inverse X, from 0 over j ascending, each product rounded before
+ * its addition, all b terms whatever their values (a non-finite x entry
+ * poisons its own block and no other); bitwise independent of k, the grid and
+ * the launch shape. y may alias x (the apply then works from a copy of x).
+ * kry_bjacobi_plan (host-only, no device): checks the partition (malformed:
+ * KRY_EINVAL; a block above 32 rows: KRY_EUNSUPPORTED, naming it) and returns
+ * the factor kernel's task list. A block of b rows belongs to a group of g =
+ * 4, 8, 16 or 32 lanes, the smallest holding it, 64 / g blocks to a wavefront:
+ * blocklist[nblocks] lists the blocks by (g, block), and task t is
+ * tasks[3 t .. 3 t + 2] = {first, count, g}, the blocks blocklist[first,
+ * first + count) of one wavefront (count = 64 / g but for the last task of a
+ * class). info[0..3] = tasks, largest block, smallest block, sum of b_i^2. Call
+ * once with null arrays to size them.
+ * kry_bjacobi_create: plan, upload, extraction and inversion (one launch per
+ * group size that occurs; the inverses stay on the device, column-major inside
+ * a block, blocks back to back). info[0] = the smallest block with a zero or
+ * non-finite pivot (-1: none; such a block is KRY_ESINGULAR and nothing is
+ * created), info[1] = the largest block, info[2] = the factor kernels' time in
+ * microseconds (HIP events).
+ * kry_bjacobi_info: info[0..5] = blocks, smallest block, largest block, bytes
+ * of the inverses, bytes of the row-to-block map and block tables, the factor
+ * kernels' microseconds.
+ * kry_bjacobi_get: the inverses copied to the host (sum of b_i^2 values of
+ * `dtype`), row-major inside a block, blocks concatenated.
+ * kry_bjacobi_apply: y = M x.
+ * kry_precond_add_bjacobi: the object as the single stage of a kry_precond
+ * (borrowed like the other stages; any other stage beside it is KRY_EINVAL),
+ * which then goes where the other factorised preconditioners go
+ * (kry_precond_apply, kry_prog_precond, kry_*_set_precond), counts one launch
+ * in kry_precond_info and takes up to 256 columns; kry_precond_fuse leaves it
+ * as it is. */
+int kry_bjacobi_plan(int64_t n, int64_t nblocks, const int32_t *starts, int64_t *info, int32_t *tasks,
+                     int32_t *blocklist);
+int kry_bjacobi_create(kry_ctx *ctx, int64_t n, int64_t nnz, const void *indptr, const void *indices, const void *data,
+                       int dtype, int itype, int64_t nblocks, const int32_t *starts, int64_t *info,
+                       kry_bjacobi **out);
+int kry_bjacobi_destroy(kry_bjacobi *B);
+int kry_bjacobi_info(const kry_bjacobi *B, int64_t *info);
+int kry_bjacobi_get(const kry_bjacobi *B, void *host);
+int kry_bjacobi_apply(kry_ctx *ctx, const kry_bjacobi *B, const kry_vec *x, kry_vec *y);
+int kry_precond_add_bjacobi(kry_precond *P, const kry_bjacobi *B);
 
 /* Batched LAPACK >= 3.10 ?lartg on device (givens.py:35-40); host arrays of
  * `count` values of `dtype`. Bitwise equal to scipy.linalg.lapack ?lartg. */

@@ -23,7 +23,7 @@ from .sparse import CsrOperator, as_device_operator, clear_operator_cache
 from .stationary import gauss_seidel, jacobi, richardson, sor, ssor
 from .chebyshev import chebyshev
 from .triangular import TriangularOperator
-from .precond import Ilu0Preconditioner, SsorPreconditioner, isai, multicolor_ordering
+from .precond import BlockJacobiPreconditioner, Ilu0Preconditioner, SsorPreconditioner, isai, multicolor_ordering
 
 __version__ = "0.1.0"
 
@@ -48,6 +48,7 @@ __all__ = [
     "TriangularOperator",
     "SsorPreconditioner",
     "Ilu0Preconditioner",
+    "BlockJacobiPreconditioner",
     "multicolor_ordering",
     "isai",
     "givens",

@@ -104,8 +104,8 @@ class Problem:
             if not _is_identity(op) and len(getattr(op, "shape", ())) != 2:
                 raise NotImplementedError(
                     f"preconditioner {name} must be None, Identity, a krylov_amd.CsrOperator, a scipy.sparse "
-                    f"matrix, a dense array or a krylov_amd.SsorPreconditioner / Ilu0Preconditioner on the MI355X "
-                    f"path (got {type(op).__name__})"
+                    f"matrix, a dense array or a krylov_amd.SsorPreconditioner / Ilu0Preconditioner / "
+                    f"BlockJacobiPreconditioner on the MI355X path (got {type(op).__name__})"
                 )
         if np.iscomplexobj(b) or (x0 is not None and np.iscomplexobj(x0)):
             raise TypeError("complex right-hand sides are outside the MI355X path")

@@ -178,6 +178,13 @@ _SIGNATURES = {
     "kry_cg_set_precond": [_vp, _i32, _vp],
     "kry_gmres_set_precond": [_vp, _i32, _vp],
     "kry_minres_set_precond": [_vp, _i32, _vp],
+    "kry_bjacobi_plan": [_i64, _i64, _vp, _ip64, _vp, _vp],
+    "kry_bjacobi_create": [_vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _i64, _vp, _ip64, _pvp],
+    "kry_bjacobi_destroy": [_vp],
+    "kry_bjacobi_info": [_vp, _ip64],
+    "kry_bjacobi_get": [_vp, _vp],
+    "kry_bjacobi_apply": [_vp, _vp, _vp, _vp],
+    "kry_precond_add_bjacobi": [_vp, _vp],
     "kry_mem_stats": [_ip64],
     "kry_mem_release": [],
 }
@@ -467,6 +474,23 @@ def ilu0_plan(indptr, indices):
     check(lib.kry_ilu0_plan(*args, ptr(level), ptr(order), ptr(launch), ptr(diag)))
     return {"levels": int(info[0]), "launches": int(info[1]), "max_level": int(info[2]), "level": level,
             "order": order, "launch": launch, "diag": diag}
+
+
+def bjacobi_plan(n, starts):
+    """Host-only check of a block-Jacobi partition and the factor kernel's
+    task list (kry_bjacobi_plan): {"tasks" (ntasks x 3: first, count, g),
+    "blocklist" (the blocks by (g, block)), "max_block", "min_block",
+    "values" (sum of b_i^2)}."""
+    starts = np.ascontiguousarray(starts, dtype=np.int32)
+    nb = starts.shape[0]
+    info = np.zeros(4, dtype=np.int64)
+    ip64 = info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    check(lib.kry_bjacobi_plan(int(n), nb, ptr(starts), ip64, None, None))
+    tasks = np.zeros((int(info[0]), 3), dtype=np.int32)
+    blocklist = np.zeros(nb, dtype=np.int32)
+    check(lib.kry_bjacobi_plan(int(n), nb, ptr(starts), ip64, ptr(tasks), ptr(blocklist)))
+    return {"tasks": tasks, "blocklist": blocklist, "max_block": int(info[1]), "min_block": int(info[2]),
+            "values": int(info[3])}
 
 
 def csr_layout(indptr):

@@ -433,7 +433,7 @@ extern "C" {
 // bits 23-25). 111: kry_csr_info_n reports the lean diagonal-offset kernel.
 // 112: descriptor classes of the diagonal-offset image (kry_csr_info_n: two
 // more values; kry_dia_class_plan; kry_csr_compare: bits 26-32).
-int kry_version(void) { return 112; }
+int kry_version(void) { return 113; }
 
 #ifndef KRY_BUILD_ID
 #define KRY_BUILD_ID "unknown"

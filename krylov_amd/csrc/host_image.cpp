@@ -1175,6 +1175,47 @@ void color_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, std::vector<in
   for (int64_t i = 0; i < n; ++i) perm[(size_t)next[(size_t)color[(size_t)i]]++] = (int32_t)i;
 }
 
+void bjacobi_plan(int64_t n, int64_t nblocks, const int32_t *starts, BjPlan &p) {
+  KRY_REQUIRE(n < INT32_MAX, KRY_EUNSUPPORTED, "the block partition indexes rows in int32");
+  KRY_REQUIRE((nblocks == 0) == (n == 0), KRY_EINVAL,
+              n == 0 ? "an empty matrix has no blocks" : "the partition has no blocks");
+  p = BjPlan();
+  p.n = n;
+  p.nblocks = nblocks;
+  if (nblocks == 0) return;
+  KRY_REQUIRE(starts[0] == 0, KRY_EINVAL, "the first block must start at row 0, not " + std::to_string(starts[0]));
+  std::vector<int32_t> bucket[4];  // g = 4 << q
+  p.min_block = kBjMaxBlock;
+  for (int64_t i = 0; i < nblocks; ++i) {
+    const int64_t s = starts[i], e = i + 1 < nblocks ? (int64_t)starts[i + 1] : n;
+    KRY_REQUIRE(s < n, KRY_EINVAL,
+                "block " + std::to_string(i) + " starts at row " + std::to_string(s) + ", past the last row");
+    KRY_REQUIRE(e > s, KRY_EINVAL,
+                "the block starts must increase strictly: block " + std::to_string(i + 1) + " starts at row " +
+                    std::to_string(e) + ", block " + std::to_string(i) + " at row " + std::to_string(s));
+    const int64_t b = e - s;
+    KRY_REQUIRE(b <= kBjMaxBlock, KRY_EUNSUPPORTED,
+                "block " + std::to_string(i) + " (from row " + std::to_string(s) + ") has " + std::to_string(b) +
+                    " rows: block-Jacobi takes blocks of at most " + std::to_string(kBjMaxBlock));
+    p.min_block = std::min<int32_t>(p.min_block, (int32_t)b);
+    p.max_block = std::max<int32_t>(p.max_block, (int32_t)b);
+    p.values += b * b;
+    int q = 0;
+    while ((4 << q) < b) ++q;
+    bucket[q].push_back((int32_t)i);
+  }
+  p.blocklist.reserve((size_t)nblocks);
+  for (int q = 0; q < 4; ++q) {
+    const int g = 4 << q;
+    const size_t per = (size_t)(64 / g);
+    for (size_t r = 0; r < bucket[q].size(); r += per) {
+      const size_t count = std::min(per, bucket[q].size() - r);
+      p.tasks.push_back(BjTask{(int32_t)p.blocklist.size(), (int32_t)count, g});
+      p.blocklist.insert(p.blocklist.end(), bucket[q].begin() + (ptrdiff_t)r, bucket[q].begin() + (ptrdiff_t)(r + count));
+    }
+  }
+}
+
 // explicit instantiations: the combinations kry_csr_create dispatches
 #define KRY_HOST_I(I)                                                                                             \
   template void check_csr<I>(int64_t, int64_t, const I *, const I *);                                            \
@@ -1443,6 +1484,26 @@ int kry_ilu0_plan(int64_t n, int64_t nnz, const void *indptr, const void *indice
   if (order) std::copy(p.tri.order.begin(), p.tri.order.end(), order);
   if (launch) std::copy(p.tri.launch.begin(), p.tri.launch.end(), launch);
   if (diag) std::copy(p.diag.begin(), p.diag.end(), diag);
+  KRY_API_END
+}
+
+int kry_bjacobi_plan(int64_t n, int64_t nblocks, const int32_t *starts, int64_t *info, int32_t *tasks,
+                     int32_t *blocklist) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(info && n >= 0 && nblocks >= 0 && (nblocks == 0 || starts), KRY_EINVAL, "bad plan arguments");
+  BjPlan p;
+  bjacobi_plan(n, nblocks, starts, p);
+  info[0] = (int64_t)p.tasks.size();
+  info[1] = p.max_block;
+  info[2] = p.min_block;
+  info[3] = p.values;
+  if (tasks)
+    for (size_t t = 0; t < p.tasks.size(); ++t) {
+      tasks[3 * t] = p.tasks[t].first;
+      tasks[3 * t + 1] = p.tasks[t].count;
+      tasks[3 * t + 2] = p.tasks[t].g;
+    }
+  if (blocklist) std::copy(p.blocklist.begin(), p.blocklist.end(), blocklist);
   KRY_API_END
 }
 

@@ -249,4 +249,25 @@ template <typename I>
 void color_plan(int64_t n, int64_t nnz, const I *ip, const I *ix, std::vector<int32_t> &color,
                 std::vector<int32_t> &perm, int64_t *ncolors, int64_t *max_rows);
 
+// Block-Jacobi (kry_bjacobi, bjacobi.hip): the partition and the task list of
+// the factor kernel. starts[nblocks] begins at 0, increases strictly and stays
+// below n; block i is rows and columns [starts[i], starts[i + 1]), n closing
+// the last one; a block holds 1 to kBjMaxBlock rows. A block of b rows belongs
+// to a lane group of g = 4, 8, 16 or 32 lanes (the smallest holding it), 64 / g
+// blocks to a wavefront: `blocklist` lists the blocks by (g, block), and task t
+// = {first, count, g} is the blocks blocklist[first, first + count) of one
+// wavefront (count = 64 / g but for the last task of a class). A malformed
+// partition is KRY_EINVAL, a block above kBjMaxBlock rows KRY_EUNSUPPORTED.
+constexpr int kBjMaxBlock = 32;
+struct BjTask {
+  int32_t first, count, g;
+};
+struct BjPlan {
+  int64_t n = 0, nblocks = 0, values = 0;  // values = sum of b_i^2
+  int32_t min_block = 0, max_block = 0;
+  std::vector<int32_t> blocklist;  // nblocks
+  std::vector<BjTask> tasks;
+};
+void bjacobi_plan(int64_t n, int64_t nblocks, const int32_t *starts, BjPlan &p);
+
 }  // namespace kry

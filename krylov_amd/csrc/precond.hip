@@ -1,8 +1,8 @@
 // Factorised preconditioners: the ILU(0) factorisation kernel, the
 // approximate-inverse kernel (ISAI, below) and the stage object kry_precond
 // (triangular solves of tri.hip and row scales, or approximate-inverse
-// products) that the solver cores and the scalar chain apply in a
-// preconditioner slot.
+// products, or the one block-Jacobi product of bjacobi.hip) that the solver
+// cores and the scalar chain apply in a preconditioner slot.
 //
 // ILU(0), in place over a copy of A's values, rows i ascending:
 //   for k in cols(i), k < i, ascending:
@@ -427,10 +427,12 @@ void vec_check(const kry_precond *P, const kry_vec *x, const kry_vec *y) {
   KRY_REQUIRE(x->n == P->n && y->n == P->n && x->k == y->k && x->dtype == P->dtype && y->dtype == P->dtype, KRY_EINVAL,
               "shape/dtype mismatch with the preconditioner");
   KRY_REQUIRE(is_pow2(x->k) && x->k <= precond_max_cols(P), KRY_EUNSUPPORTED,
-              "a factorised preconditioner handles up to 64 columns (256 with approximate-inverse solves)");
+              "a factorised preconditioner handles up to 64 columns (256 with approximate-inverse solves or "
+              "block-Jacobi)");
 }
 
 bool is_isai(const kry_precond *P) { return !P->stages.empty() && P->stages[0].isai_w != nullptr; }
+bool is_bjacobi(const kry_precond *P) { return !P->stages.empty() && P->stages[0].bj != nullptr; }
 
 // the blocks between the stages, grown to k columns
 void isai_scratch(const kry_precond *P, int k) {
@@ -518,12 +520,16 @@ static void fuse_plan(kry_precond *P) {
   }
 }
 
-int precond_max_cols(const kry_precond *P) { return is_isai(P) ? kMaxCols : 64; }
+int precond_max_cols(const kry_precond *P) { return is_isai(P) || is_bjacobi(P) ? kMaxCols : 64; }
 
 static int precond_launches(const kry_precond *P) {
   int count = 0;
   for (size_t i = 0; i < P->stages.size(); ++i) {
     const kry_precond::Stage &s = P->stages[i];
+    if (s.bj) {
+      count += 1;  // the batched block product
+      continue;
+    }
     if (s.isai_w) {
       count += 1 + 2 * s.sweeps;  // the SpMVs
       continue;
@@ -542,6 +548,7 @@ static int precond_launches(const kry_precond *P) {
 void precond_stages(const kry_precond *P, int k, const void *src, void *dst, const Ctrl *ctrl, int step,
                     hipStream_t st) {
   KRY_REQUIRE(!P->stages.empty(), KRY_EINVAL, "a preconditioner without stages");
+  if (is_bjacobi(P)) return bjacobi_apply_raw(P->stages[0].bj, k, src, dst, ctrl, step, st);
   if (is_isai(P)) {
     if (P->dtype == KRY_F64)
       isai_stages<double>(P, k, static_cast<const double *>(src), static_cast<double *>(dst), ctrl, step, st);
@@ -581,7 +588,9 @@ void precond_check(const kry_precond *P, const kry_csr *A, int64_t n, int k, int
   KRY_REQUIRE(P->n == n, KRY_EINVAL, "preconditioner shape does not match the operator");
   KRY_REQUIRE(P->dtype == dtype, KRY_EINVAL, "a factorised preconditioner's dtype must be the vectors'");
   KRY_REQUIRE(!P->stages.empty(), KRY_EINVAL, "a preconditioner without stages");
-  if (is_isai(P))
+  if (is_bjacobi(P))
+    KRY_REQUIRE(is_pow2(k) && k <= kMaxCols, KRY_EUNSUPPORTED, "a block-Jacobi preconditioner handles up to 256 columns");
+  else if (is_isai(P))
     KRY_REQUIRE(is_pow2(k) && k <= kMaxCols, KRY_EUNSUPPORTED,
                 "a factorised preconditioner with approximate-inverse solves handles up to 256 columns");
   else
@@ -658,7 +667,8 @@ int kry_precond_fuse(kry_precond *P) {
   KRY_API_BEGIN
   KRY_REQUIRE(P, KRY_EINVAL, "null argument");
   KRY_REQUIRE(!P->stages.empty(), KRY_EINVAL, "a preconditioner without stages");
-  P->fused = P->fuse_allowed && !is_isai(P);  // approximate-inverse stages have no levels to fuse
+  // approximate-inverse stages and a block-Jacobi stage have no levels to fuse
+  P->fused = P->fuse_allowed && !is_isai(P) && !is_bjacobi(P);
   if (P->fused) fuse_plan(P);
   KRY_API_END
 }
@@ -694,6 +704,7 @@ int kry_precond_add_tri(kry_precond *P, const kry_tri *T) {
   KRY_REQUIRE(n == P->n && dtype == P->dtype, KRY_EINVAL, "shape/dtype mismatch with the preconditioner");
   KRY_REQUIRE(P->stages.size() < 8, KRY_EINVAL, "at most 8 stages");
   KRY_REQUIRE(!is_isai(P), KRY_EINVAL, "a preconditioner of approximate-inverse stages takes no other stage");
+  KRY_REQUIRE(!is_bjacobi(P), KRY_EINVAL, "a block-Jacobi preconditioner takes no other stage");
   kry_precond::Stage s;
   s.tri = T;
   P->stages.push_back(s);
@@ -707,6 +718,7 @@ int kry_precond_add_scale(kry_precond *P, const kry_vec *d) {
               "the scale must be (n,) of the preconditioner's dtype");
   KRY_REQUIRE(P->stages.size() < 8, KRY_EINVAL, "at most 8 stages");
   KRY_REQUIRE(!is_isai(P), KRY_EINVAL, "a preconditioner of approximate-inverse stages takes no other stage");
+  KRY_REQUIRE(!is_bjacobi(P), KRY_EINVAL, "a block-Jacobi preconditioner takes no other stage");
   kry_precond::Stage s;
   s.scale = d->d;
   P->stages.push_back(s);
@@ -734,6 +746,20 @@ int kry_precond_add_isai(kry_precond *P, const kry_csr *W, const kry_csr *T, int
   s.isai_t = T;
   s.sweeps = sweeps;
   s.scale = scale ? scale->d : nullptr;
+  P->stages.push_back(s);
+  KRY_API_END
+}
+
+int kry_precond_add_bjacobi(kry_precond *P, const kry_bjacobi *B) {
+  KRY_API_BEGIN
+  KRY_REQUIRE(P && B, KRY_EINVAL, "null argument");
+  int64_t n = 0;
+  int dtype = 0;
+  bjacobi_shape(B, &n, &dtype);
+  KRY_REQUIRE(n == P->n && dtype == P->dtype, KRY_EINVAL, "shape/dtype mismatch with the preconditioner");
+  KRY_REQUIRE(P->stages.empty(), KRY_EINVAL, "a block-Jacobi stage is the only stage of its preconditioner");
+  kry_precond::Stage s;
+  s.bj = B;
   P->stages.push_back(s);
   KRY_API_END
 }

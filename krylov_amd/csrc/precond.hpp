@@ -9,6 +9,7 @@
 #include "solver_common.hpp"
 
 struct kry_tri;
+struct kry_bjacobi;
 
 // A stage is a triangular solve (tri), a row scale by an (n,) device vector
 // of the preconditioner's dtype (scale), or an approximate-inverse solve
@@ -16,13 +17,16 @@ struct kry_tri;
 // folded into the last product's store when the stage carries a scale. The
 // stages are borrowed: the caller keeps the kry_tri / kry_vec / kry_csr
 // handles alive while the preconditioner is. A preconditioner holds solves
-// and scales or approximate-inverse stages, never both.
+// and scales or approximate-inverse stages, never both. A block-Jacobi stage
+// (bj: one batched block product, bjacobi.hip) is the only stage of its
+// preconditioner.
 struct kry_precond {
   struct Stage {
     const kry_tri *tri = nullptr;
     const void *scale = nullptr;
     const kry_csr *isai_w = nullptr, *isai_t = nullptr;  // isai_t: null without sweeps
     int sweeps = 0;
+    const kry_bjacobi *bj = nullptr;
   };
   kry_ctx *ctx = nullptr;
   int64_t n = 0;
@@ -69,12 +73,16 @@ bool tri_boundary_match(const kry_tri *T, const kry_tri *next);
 void tri_boundary(const kry_tri *T, const kry_tri *next, int k, const void *y, void *x, const void *scale,
                   const Ctrl *ctrl, int step, hipStream_t st);
 int tri_launches(const kry_tri *T, bool skip_first, bool skip_last);
+// bjacobi.hip: y = B x on raw n x k blocks (k a power of two <= kMaxCols; y may alias x)
+void bjacobi_apply_raw(const kry_bjacobi *B, int k, const void *x, void *y, const Ctrl *ctrl, int step,
+                       hipStream_t st);
+void bjacobi_shape(const kry_bjacobi *B, int64_t *n, int *dtype);
 // precond.hip: dst = P src, stage by stage (the first stage reads src, the
 // others work in place on dst; dst may alias src)
 void precond_stages(const kry_precond *P, int k, const void *src, void *dst, const Ctrl *ctrl, int step,
                     hipStream_t st);
 // the most columns an apply takes: kMaxCols for approximate-inverse stages
-// (SpMVs), 64 for triangular solves
+// (SpMVs) and for a block-Jacobi stage, 64 for triangular solves
 int precond_max_cols(const kry_precond *P);
 // what every set_precond of the cores checks
 void precond_check(const kry_precond *P, const kry_csr *A, int64_t n, int k, int dtype);

@@ -38,6 +38,14 @@ The upper factor takes ``W_U = isai(U^T)^T``, the right inverse, so that
 stays symmetric. An apply is ``2 + 4 sweeps`` SpMV launches (SSOR's row scale
 goes into the store of the lower stage's last product) and takes up to 256
 columns; W and T are device matrices that are never renumbered.
+
+``BlockJacobiPreconditioner`` is the one object that is a single launch by
+construction: ``M = blockdiag(A_11, ..., A_mm)^-1`` over a partition of the
+rows into blocks of 1 to 32, the blocks inverted once on the device
+(``kry_bjacobi_create``: Gauss-Jordan with row pivoting, bitwise the
+sequential loop), an apply one batched dense block product for up to 256
+columns. It pays on systems with several unknowns per node
+(``problems.multidof``).
 """
 import ctypes
 import time
@@ -425,3 +433,88 @@ class Ilu0Preconditioner(_Factored):
         """The plans of the two solves ("stages") and the factorisation's own
         ("factor": {"levels", "launches", "max_level"})."""
         return {"factor": dict(self._plan), **super().layout()}
+
+
+class BlockJacobiPreconditioner(_Factored):
+    """``M = blockdiag(A_11, ..., A_mm)^-1``: the diagonal blocks of A over a
+    partition of its rows, inverted once on the device; an apply is one
+    launch, a batched dense block product, for up to 256 columns.
+
+    ``block_size=b``: blocks of b consecutive rows (the last may be smaller);
+    ``blocks=starts``: block i is rows [starts[i], starts[i + 1]), with
+    starts[0] = 0, strictly increasing, every start below n, and n closing
+    the last block. Exactly one of the two; a block holds 1 to 32 rows
+    (``NotImplementedError`` naming the block above that). Block i is the
+    dense array of A's stored entries inside it; its inverse is in-place
+    Gauss-Jordan with row pivoting in ``dtype`` scalars, and the apply sums
+    ``X[r, j] * x[j]`` over j ascending: both bitwise the sequential loops
+    (include/krylov_hip.h). A block with a zero or non-finite pivot raises
+    ``LinAlgError`` naming the smallest such block and its first row.
+    ``A``: scipy.sparse matrix or dense array; ``dtype``: the dtype of the
+    vectors it will precondition (default A's)."""
+
+    max_cols = 256
+
+    def __init__(self, A, block_size=None, blocks=None, dtype=None, device=None):
+        if (block_size is None) == (blocks is None):
+            raise ValueError("BlockJacobiPreconditioner takes exactly one of block_size= and blocks=")
+        csr, dt = _canonical(A, "BlockJacobiPreconditioner", dtype)
+        n, nnz = csr.shape[0], int(csr.nnz)
+        if nnz >= 2**31 - 1 or n >= 2**31 - 1:
+            raise NotImplementedError("block-Jacobi indexes entries in int32")
+        if block_size is not None:
+            if int(block_size) != block_size or block_size < 1:
+                raise ValueError(f"block_size must be an integer >= 1, not {block_size!r}")
+            if block_size > 32:
+                raise NotImplementedError(f"block_size={int(block_size)}: block-Jacobi takes blocks of at most 32 rows")
+            starts = np.arange(0, n, int(block_size), dtype=np.int32)
+        else:
+            raw = np.asarray(blocks)
+            if raw.ndim != 1 or (raw.size and not np.issubdtype(raw.dtype, np.integer)):
+                raise ValueError("blocks must be a 1-D array of integer row indices (the first row of every block)")
+            if raw.size and (raw.min() < 0 or raw.max() >= 2**31):
+                raise ValueError("blocks must hold row indices in [0, n)")
+            starts = np.ascontiguousarray(raw, dtype=np.int32)
+        ctx = get_context(device)
+        indptr = np.ascontiguousarray(csr.indptr, dtype=np.int32)
+        indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
+        data = np.ascontiguousarray(csr.data, dtype=dt)
+        info = np.zeros(3, dtype=np.int64)
+        h = ctypes.c_void_p()
+        t0 = time.perf_counter()
+        check(lib.kry_bjacobi_create(ctx.handle, n, nnz, _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data),
+                                     _lib.dtype_code(dt), _lib.KRY_I32, starts.shape[0], _lib.ptr(starts),
+                                     info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(h)))
+        # plan, uploads, the factor kernels and the wait for them (tools/bench_precond.py)
+        self.factor_seconds = time.perf_counter() - t0
+        self.factor_kernel_seconds = float(info[2]) * 1e-6
+        self._bj = h
+        self._bj_fin = _lib.own(self, lib.kry_bjacobi_destroy, h)
+        self.blocks = np.concatenate([starts, np.array([n], dtype=np.int32)])
+        self._begin(n, dt, ctx, [], "natural", None, None)
+        check(lib.kry_precond_add_bjacobi(self.handle, h))
+
+    def inverse_blocks(self):
+        """The inverses as the device holds them: a list of (b_i, b_i) arrays."""
+        sizes = np.diff(self.blocks).astype(np.int64)
+        flat = np.zeros(max(int(np.sum(sizes * sizes)), 1), dtype=self.dtype)
+        check(lib.kry_bjacobi_get(self._bj, _lib.ptr(flat)))
+        offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
+        return [flat[offs[i]:offs[i + 1]].reshape(int(b), int(b)).copy() for i, b in enumerate(sizes)]
+
+    def layout(self):
+        """{"blocks" (count), "block_sizes": (min, max), "value_bytes" (the
+        inverses), "map_bytes" (the row-to-block map and the block tables),
+        "launches": 1, "factor_kernel_seconds", "solve": "exact", "fused":
+        False, "ordering": "natural"}."""
+        info = np.zeros(6, dtype=np.int64)
+        check(lib.kry_bjacobi_info(self._bj, info.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        pin = np.zeros(5, dtype=np.int64)
+        check(lib.kry_precond_info(self.handle, pin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return {"blocks": int(info[0]), "block_sizes": (int(info[1]), int(info[2])), "value_bytes": int(info[3]),
+                "map_bytes": int(info[4]), "launches": int(pin[0]), "factor_kernel_seconds": float(info[5]) * 1e-6,
+                "solve": self.solve_kind, "sweeps": 0, "fused": bool(pin[1]), "ordering": "natural", "colors": None}
+
+    def close(self):
+        self._fin()
+        self._bj_fin()

@@ -21,6 +21,7 @@ __all__ = [
     "shifted_lap3d_weighted",
     "csr_sha256",
     "diag100",
+    "multidof",
 ]
 
 
@@ -189,6 +190,41 @@ def permuted_sym(A, seed=0):
     data = A.data[src[order]]
     it = A.indptr.dtype if nnz < 2**31 else np.int64
     return scipy.sparse.csr_matrix((data, indices, indptr.astype(it)), shape=A.shape)
+
+
+def multidof(m=24, d=4, seed=0, sym=True):
+    """A system with d unknowns per node of an m x m grid:
+    ``kron(poisson2d(m), S) + block_diag(K_i)``, n = m^2 d, canonical float64
+    CSR with int32 indices. ``S = G G^T + 0.1 I`` scaled to unit 2-norm (G a
+    d x d standard normal draw) couples the unknowns of a node and of its
+    neighbours; ``K_i = 0.005 H_i H_i^T / d`` (H_i standard normal, per node)
+    makes the nodes differ. Every draw comes from one ``default_rng(seed)``: G
+    first, then the H_i in node order. SPD for ``sym=True``; ``sym=False``
+    adds a strictly upper part to S (0.05 U(-1, 1), drawn after G) and to
+    every K_i (0.001 U(-1, 1), drawn after H_i). Unknown j of node i is row
+    i d + j, so blocks of d are the nodes (block-Jacobi's natural partition)."""
+    rng = np.random.default_rng(seed)
+    G = rng.standard_normal((d, d))
+    S = G @ G.T + 0.1 * np.eye(d)
+    S = S / np.linalg.norm(S, 2)
+    if not sym:
+        S = S + 0.05 * np.triu(rng.uniform(-1.0, 1.0, (d, d)), 1)
+    nodes = m * m
+    K = np.empty((nodes, d, d))
+    for i in range(nodes):
+        H = rng.standard_normal((d, d))
+        K[i] = 0.005 * (H @ H.T) / d
+        if not sym:
+            K[i] = K[i] + 0.001 * np.triu(rng.uniform(-1.0, 1.0, (d, d)), 1)
+    A = scipy.sparse.kron(poisson2d(m), scipy.sparse.csr_matrix(S), format="csr")
+    A = A + scipy.sparse.block_diag(list(K), format="csr")
+    A = scipy.sparse.csr_matrix(A)
+    A.sum_duplicates()
+    A.sort_indices()
+    if A.nnz < 2**31:
+        A.indices = A.indices.astype(np.int32)
+        A.indptr = A.indptr.astype(np.int32)
+    return A
 
 
 def diag100(n=100):

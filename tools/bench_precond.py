@@ -31,6 +31,19 @@ without a preconditioner and with each one (cg: M; gmres: Mr):
                  tol = 1e-8 (after a two-step call that loads the code objects
                  and caches the operator's upload), capped at MAX_CG steps /
                  MAX_CYCLES cycles
+The block-Jacobi leg (BlockJacobiPreconditioner; --bjacobi runs it alone,
+--no-bjacobi leaves it out) is a section of its own, "bjacobi": on
+multidof(700, 4) (n = 1.96 M, several unknowns per node) CG without a
+preconditioner, with the point-Jacobi matrix diag(A)^-1 as M and with
+block_size=4; on poisson2d(1000) the same with block_size=8; on
+random_nonsym(2_000_000) gmres(30) without, with diag(A)^-1 and with
+block_size=8 as Mr. Per workload spmv_ms; per preconditioner setup_s (the
+constructor), factor_s (kry_bjacobi_create: plan, uploads, kernels),
+factor_kernel_s (the factor kernels alone, HIP events), ms_per_apply as above
+(the point-Jacobi matrix: its SpMV), blocks, block_sizes, value_bytes; per
+solve steps, success, wall_s, once with b = ones ("solves", as the other legs)
+and once with b = default_rng(3).standard_normal(n) ("solves_rng3", the
+right-hand side of the parity cases).
 No threshold is attached: the tool records what it measures.
 """
 import argparse
@@ -121,6 +134,52 @@ def solve_gmres(A, b, Mr):
             "wall_s": wall, "final_relres": float(np.max(infos[-1].resnorms[-1])) / first}
 
 
+def build_bjacobi(name, A, bs):
+    import krylov_amd
+
+    t0 = time.perf_counter()
+    P = krylov_amd.BlockJacobiPreconditioner(A, block_size=bs)
+    out = {"setup_s": time.perf_counter() - t0, "factor_s": P.factor_seconds,
+           "factor_kernel_s": P.factor_kernel_seconds}
+    out["ms_per_apply"], out["ms_regions"] = time_apply(P)
+    lay = P.layout()
+    out.update({k: lay[k] for k in ("blocks", "block_sizes", "value_bytes", "map_bytes", "launches")})
+    print(f"  {name}: setup {out['setup_s']:.2f} s, factor kernel {out['factor_kernel_s'] * 1e3:.3f} ms, "
+          f"apply {out['ms_per_apply']:.3f} ms", file=sys.stderr, flush=True)
+    return P, out
+
+
+def workload_bjacobi(name, A, spd, bs):
+    """none / point Jacobi / block-Jacobi on one matrix: cg (M) on an SPD one,
+    gmres(30) (Mr) otherwise."""
+    import krylov_amd
+    import scipy.sparse
+
+    n = A.shape[0]
+    b = np.ones(n)
+    out = {"n": n, "nnz": int(A.nnz), "block_size": bs, "precond": {}, "solves": {}}
+    out["spmv_ms"], _ = time_apply(krylov_amd.as_device_operator(A))
+    t0 = time.perf_counter()
+    J = scipy.sparse.diags(1.0 / A.diagonal(), format="csr")
+    Jop = krylov_amd.CsrOperator(J, like=krylov_amd.as_device_operator(A))
+    out["precond"]["jacobi"] = {"setup_s": time.perf_counter() - t0}
+    out["precond"]["jacobi"]["ms_per_apply"], out["precond"]["jacobi"]["ms_regions"] = time_apply(Jop)
+    P, out["precond"][f"bjacobi{bs}"] = build_bjacobi(f"{name} bjacobi{bs}", A, bs)
+    sname, fn = ("cg", solve_cg) if spd else (f"gmres({RESTART})", solve_gmres)
+    # b = ones as in the other legs, and the right-hand side of the parity cases (tests/blockjacobi_cases.py)
+    for key, rhs in (("solves", b), ("solves_rng3", np.random.default_rng(3).standard_normal(n))):
+        out[key] = {}
+        for pname, M in (("none", None), ("jacobi", J), (f"bjacobi{bs}", P)):
+            with np.errstate(all="ignore"):
+                try:
+                    r = fn(A, rhs, M)
+                except Exception as e:  # recorded, not hidden
+                    r = {"error": f"{type(e).__name__}: {e}"}
+            out[key][f"{sname}/{pname}"] = r
+            print(f"  {name} {key} {sname}/{pname}: {r}", file=sys.stderr, flush=True)
+    return out
+
+
 def workload(name, A, spd):
     import krylov_amd
 
@@ -159,6 +218,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--small", action="store_true", help="tiny sizes (a rehearsal of the script, not a measurement)")
+    ap.add_argument("--bjacobi", action="store_true", help="the block-Jacobi leg alone")
+    ap.add_argument("--no-bjacobi", action="store_true", help="everything but the block-Jacobi leg")
     args = ap.parse_args()
     from krylov_amd import _lib, problems
 
@@ -167,8 +228,16 @@ def main():
     m, n = (60, 20_000) if args.small else (1000, 2_000_000)
     res = {"bench": "precond", "regions": REGIONS, "tol": TOL, "max_cg": MAX_CG, "max_cycles": MAX_CYCLES,
            "restart": RESTART, "build_id": _lib.build_id(), "workloads": {}}
-    res["workloads"][f"poisson2d({m})"] = workload("poisson2d", problems.poisson2d(m), True)
-    res["workloads"][f"random_nonsym({n})"] = workload("random_nonsym", problems.random_nonsym(n), False)
+    if not args.bjacobi:
+        res["workloads"][f"poisson2d({m})"] = workload("poisson2d", problems.poisson2d(m), True)
+        res["workloads"][f"random_nonsym({n})"] = workload("random_nonsym", problems.random_nonsym(n), False)
+    if not args.no_bjacobi:
+        md = 40 if args.small else 700
+        res["bjacobi"] = {
+            f"multidof({md}, 4)": workload_bjacobi("multidof", problems.multidof(md, 4), True, 4),
+            f"poisson2d({m})": workload_bjacobi("poisson2d", problems.poisson2d(m), True, 8),
+            f"random_nonsym({n})": workload_bjacobi("random_nonsym", problems.random_nonsym(n), False, 8),
+        }
     line = json.dumps(res)
     print(line)
     if args.out:
