@@ -25,6 +25,8 @@ import numpy as np
 import pytest
 import scipy.sparse
 
+from tests.spmv_patterns import adversarial as _adversarial
+
 pytestmark = pytest.mark.gpu
 
 
@@ -32,28 +34,6 @@ def _bits(a, b):
     a, b = np.asarray(a), np.asarray(b)
     assert a.dtype == b.dtype and a.shape == b.shape
     np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _adversarial(dtype, seed=0, n=200_003, long_rows=True):
-    """Unsorted rows, duplicates, explicit zeros, empty rows, rows longer than
-    one 16-entry run (whole slices of them: the image refuses more than 1.25x
-    the SELL-64 slots), values and x over a wide exponent range."""
-    rng = np.random.default_rng(seed)
-    lens = rng.integers(0, 12, n)
-    if long_rows:
-        lens[1024:1280] = rng.integers(17, 70, 256)
-        lens[2048:2176] = rng.integers(30, 34, 128)
-    lens[100:130] = 0
-    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    cols = rng.integers(0, n, indptr[-1]).astype(np.int32)  # unsorted, wide spans
-    dup = rng.integers(0, indptr[-1], indptr[-1] // 20)
-    cols[dup[1:]] = cols[dup[:-1]]
-    e = 30 if dtype == np.float64 else 8
-    vals = (rng.standard_normal(indptr[-1]) * 10.0 ** rng.integers(-e, e, indptr[-1])).astype(dtype)
-    vals[::13] = 0.0
-    A = scipy.sparse.csr_matrix((vals, cols, indptr), shape=(n, n))
-    x = (rng.standard_normal(n) * 10.0 ** rng.integers(-e, e, n)).astype(dtype)
-    return A, x
 
 
 @pytest.mark.parametrize("rs1", ["0", "1", "2"])
